@@ -8,8 +8,17 @@ in HBM; one RCCL reduce(sum) of the films to rank 0 per batch is inside the
 timed region.  value = (closest + shadow traversals of all ranks) / max-rank
 wall time, in Mrays/s.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...   (the driver's N > 1 form)
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full
+adds the legs that take runs of their own (the Extra JSON keys below: the
+work-counting replay behind `roofline`, the other traversal mode, the CPU
+baselines); --no-count / --no-compare / --no-cpu drop single legs of it.
+--dump-outputs DIR writes what the timed steps returned (rank 0: film.npy, the
+reduced H x W x 3 float32 film after the last step; ray_counts.npy, float64
+[closest, shadow] of this rank) right after them; the inputs are a pure
+function of the arguments (counter RNG), so two builds compare output for output.
 
 --config picks the SURVEY.md 8(d) configuration: c2 (default; the BASELINE.json
 metric), c3 (cbox + dragon PT, one step = one sample index of a 512-spp
@@ -17,7 +26,7 @@ stratified render), c4 (the 1M-triangle synthetic torus, BDPT), vcm (torus.scene
 with VertexCM, SURVEY 8(f) item 4: one step = one VCM iteration, merge radius
 0.003 x sceneRadius shrinking with the global iteration index).
 
-Extra JSON keys: spp_per_sec, roofline (dominant kernel = KD traversal, HIP
+Extra JSON keys: spp_per_sec; with --full: roofline (dominant kernel = KD traversal, HIP
 events on the context stream), cpu_baseline (the reference itself, built from
 its sources by oracle/Makefile, one thread, the same scene at reduced
 resolution), cpu_port (the oracle's C port, MT-serial, one thread, a bounded
@@ -225,13 +234,16 @@ def main():
                     help="c2 (default, the BASELINE metric), c3 PT, c4 1M triangles, vcm VertexCM, sph spheres")
     ap.add_argument("--spp", type=int, default=512, help="c3: stratification grid of the PT render")
     ap.add_argument("--cpu-paths", type=int, default=1000000)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-count", action="store_true", help="skip the work-counting replay")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the work-counting replay (roofline), the other traversal "
+                         "mode (other_trace) and the CPU baselines; off by default")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-count", action="store_true", help="--full without the work-counting replay")
     ap.add_argument("--trace", choices=["auto", "reference", "bvh"], default="auto",
                     help="traversal: the reference's KD walk, or the verified BVH search (same (t, primitive) "
                          "answers, DESIGN.md section 4b); auto = the faster one: bvh for every config")
     ap.add_argument("--no-compare", action="store_true",
-                    help="skip the single-GPU comparison run in the other traversal mode")
+                    help="--full without the single-GPU comparison run in the other traversal mode")
     ap.add_argument("--no-cut", action="store_true",
                     help="c3/vcm: shadow rays run to the end of the walk (no occlusion cutoff)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
@@ -241,6 +253,9 @@ def main():
                     help="global index of rank 0's first iteration (sample): one rank's shard of a bigger job, "
                          "e.g. --config c4 --steps 512 --iter-begin 512 = rank 1 of SURVEY 8(d) C5")
     ap.add_argument("--dump-film", default=None, help="rank 0 writes the reduced film here (.npy, float32 H x W x 3)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the timed steps' outputs to DIR: film.npy (float32 H x W x 3, the reduced "
+                         "film after the last step) and ray_counts.npy (float64 [closest, shadow])")
     ap.add_argument("--rccl-self-check", action="store_true",
                     help="N = 1 with --backend nccl: run the library's RCCL communicator and film reduce anyway "
                          "(the N > 1 code path on one GPU; a test of it)")
@@ -337,6 +352,16 @@ def main():
     if args.dump_film and rank == 0:
         import numpy as np
         np.save(args.dump_film, film.cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        f = film.cpu().numpy()
+        if f.nbytes > 48 << 20:  # a frame beyond 48 MB: a fixed, seeded sample of its pixels
+            pix = np.sort(np.random.default_rng(5489).choice(H * W, (48 << 20) // 12, replace=False))
+            f = f.reshape(H * W, 3)[pix]
+        np.save(os.path.join(args.dump_outputs, "film.npy"), f)
+        np.save(os.path.join(args.dump_outputs, "ray_counts.npy"),
+                np.array([st.closest_rays, st.shadow_rays], dtype=np.float64))
     rays = st.closest_rays + st.shadow_rays
     trace_ms = st.kernel_ms[native.K_TRACE]
     trace_launches = st.kernel_launches[native.K_TRACE]
@@ -346,7 +371,7 @@ def main():
     red_min, red_max = wdist.min_max(reduce_s, dist, film.device)
 
     roofline = None
-    if not args.no_count and rank == 0:
+    if args.full and not args.no_count and rank == 0:
         # replay the same iterations with per-traversal counters (identical ray set:
         # the counter RNG makes the work a pure function of (seed, iteration, path))
         _, cst = render(it0, K, count_work=1, film=None)
@@ -440,7 +465,7 @@ def main():
             roofline["bvh"] = bvh
 
     other = None
-    if rank == 0 and world == 1 and not args.no_compare:
+    if args.full and rank == 0 and world == 1 and not args.no_compare:
         # the same K steps in the other traversal mode (same rays, same answers),
         # timed the same way, for the line's `other_trace`
         o_mode = "reference" if trace == "bvh" else "bvh"
@@ -459,7 +484,7 @@ def main():
             other = {"trace": o_mode, "error": str(e)}
 
     cpu = port = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         # the reference on the full frame for C2 (the config's
         # resolution, fewer iterations: 1 iteration is ~35-40 s of one core);
         # the 1M-triangle C4 at a quarter of it per axis

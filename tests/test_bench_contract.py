@@ -1,7 +1,7 @@
 """bench.py's output contract on the GPU box (`-m gpu`): one JSON line with the
 driver's keys, a roofline object whose frac is achieved / peak in (0, 1], and the
 whole-job value consistent with rays_per_step / ms_per_step.  Short runs
-(2 timed steps, no CPU leg) of every configuration, each in a child process.
+(--full, 2 timed steps, no CPU leg) of every configuration, each in a child process.
 On a host without a GPU (CPU suite) it must fail loudly: no CPU fallback.
 """
 import json
@@ -19,7 +19,7 @@ ROOF = ("bound", "achieved", "peak", "unit", "frac", "traffic")
 
 
 def run_bench(*args):
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu", *args],
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--no-cpu", *args],
                          cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]
@@ -52,6 +52,33 @@ def test_bench_line(cfg):
     assert 0 < r["frac_step"] <= r["frac"] * 1.001
     if r.get("hbm"):
         assert 0 < r["hbm"]["frac"] <= 1 and r["hbm"]["peak"] == 8000.0
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline keys only (no replay, no
+    other traversal mode, no CPU leg), and --dump-outputs writes what the timed
+    steps returned: the film and this rank's ray counts."""
+    import numpy as np
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--width", "192",
+                          "--height", "112", "--dump-outputs", str(tmp_path / "o")],
+                         cwd=ROOT, capture_output=True, text=True, timeout=240)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in KEYS:
+        assert k in d, k
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    assert "other_trace" not in d and "cpu_port" not in d
+    assert sorted(os.listdir(tmp_path / "o")) == ["film.npy", "ray_counts.npy"]
+    film = np.load(tmp_path / "o" / "film.npy")
+    assert film.dtype == np.float32 and film.shape == (112, 192, 3)
+    assert np.isfinite(film).all() and film.max() > 0
+    counts = np.load(tmp_path / "o" / "ray_counts.npy")
+    assert counts.dtype == np.float64 and counts.shape == (2,)
+    assert counts.sum() == pytest.approx(d["rays_per_step"] * 2, abs=2)
 
 
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="a GPU may be visible here")
