@@ -72,6 +72,28 @@ __device__ __forceinline__ void bqst3(float* s, int p, int k, V3 v) {
   r[1] = v.y;
   r[2] = v.z;
 }
+// The record as its two 16-byte halves, a = (thr, dVCM), b = (dVC, ctr, pack,
+// pix): a vertex reads it with two loads issued with its other inputs
+// (vertex_inputs) and writes back the half or halves that changed.  A path's
+// record is touched only by the thread shading that path's vertex (the other
+// pass reads lvc / cvc), so whole-record stores race with nothing.
+struct BqRec {
+  float4 a, b;
+};
+__device__ __forceinline__ BqRec bq_load(const float* s, int p) {
+  const float4* r = reinterpret_cast<const float4*>(s) + 2 * size_t(p);
+  return BqRec{r[0], r[1]};
+}
+__device__ __forceinline__ float4 bq_half_a(V3 thr, float dvcm) { return make_float4(thr.x, thr.y, thr.z, dvcm); }
+__device__ __forceinline__ float4 bq_half_b(float dvc, uint32_t ctr, int pack, int pix) {
+  return make_float4(dvc, __uint_as_float(ctr), __int_as_float(pack), __int_as_float(pix));
+}
+__device__ __forceinline__ void bq_store_a(float* s, int p, float4 a) {
+  reinterpret_cast<float4*>(s)[2 * size_t(p)] = a;
+}
+__device__ __forceinline__ void bq_store_b(float* s, int p, float4 b) {
+  reinterpret_cast<float4*>(s)[2 * size_t(p) + 1] = b;
+}
 __device__ __forceinline__ int bq_pack(int len, int nspec, int cnt) { return len | (nspec << 8) | (cnt << 16); }
 __device__ __forceinline__ int bq_len(int w) { return w & 255; }
 __device__ __forceinline__ int bq_nspec(int w) { return (w >> 8) & 255; }
@@ -84,48 +106,58 @@ constexpr int kLightAlive = 0x80;  // BdptBuf::lvc
 // a sphere, the position), the local wi and the material, and stored_bsdf
 // rebuilds them with the operations the vertex itself ran (prim_normal,
 // bsdf_probs), to the same floats.
-//   BV_PACK = len | nspec << 8 | material << 16 (int16: emitters are < 0)
+// A record moves as four 16-byte words (BvRec): written whole by store_vertex,
+// read whole once per slot before any field is looked at, and passed by value.
+//   BV_PACK = len | nspec << 8; the material is a word of its own (BV_MAT:
+//   emitters are -(light + 1), any face count)
 enum : int { BV_POS = 0, BV_WI = 3, BV_THR = 6, BV_DVCM = 9, BV_DVC = 10, BV_PRIM = 11, BV_PACK = 12, BV_PIX = 13,
-             BV_WORDS = 16 };
-__device__ __forceinline__ float& bvf(float* s, int i, int k) { return s[size_t(i) * BV_WORDS + k]; }
-__device__ __forceinline__ int& bvi(float* s, int i, int k) {
-  return reinterpret_cast<int*>(s)[size_t(i) * BV_WORDS + k];
+             BV_MAT = 14, BV_WORDS = 16 };
+struct BvRec {
+  float4 a, b, c, d;  // words 0-3, 4-7, 8-11, 12-15
+};
+__device__ __forceinline__ BvRec bv_load(const float* s, int i) {
+  const float4* r = reinterpret_cast<const float4*>(s) + 4 * size_t(i);
+  return BvRec{r[0], r[1], r[2], r[3]};
 }
-__device__ __forceinline__ V3 bvld3(const float* s, int i, int k) {
-  const float* r = s + size_t(i) * BV_WORDS + k;
-  return v3(r[0], r[1], r[2]);
-}
-__device__ __forceinline__ void bvst3(float* s, int i, int k, V3 v) {
-  float* r = s + size_t(i) * BV_WORDS + k;
-  r[0] = v.x;
-  r[1] = v.y;
-  r[2] = v.z;
-}
-__device__ __forceinline__ int bv_pack(int len, int nspec, int mat) {
-  return len | (nspec << 8) | static_cast<int>(static_cast<uint32_t>(mat) << 16);
-}
-__device__ __forceinline__ int bv_len(int w) { return w & 255; }
-__device__ __forceinline__ int bv_nspec(int w) { return (w >> 8) & 255; }
-__device__ __forceinline__ int bv_mat(int w) { return w >> 16; }  // arithmetic: the sign comes back
+__device__ __forceinline__ V3 bv_pos(const BvRec& r) { return v3(r.a.x, r.a.y, r.a.z); }
+__device__ __forceinline__ V3 bv_wi(const BvRec& r) { return v3(r.a.w, r.b.x, r.b.y); }
+__device__ __forceinline__ V3 bv_thr(const BvRec& r) { return v3(r.b.z, r.b.w, r.c.x); }
+__device__ __forceinline__ float bv_dvcm(const BvRec& r) { return r.c.y; }
+__device__ __forceinline__ float bv_dvc(const BvRec& r) { return r.c.z; }
+__device__ __forceinline__ int bv_prim(const BvRec& r) { return __float_as_int(r.c.w); }
+__device__ __forceinline__ int bv_len(const BvRec& r) { return __float_as_int(r.d.x) & 255; }
+__device__ __forceinline__ int bv_nspec(const BvRec& r) { return (__float_as_int(r.d.x) >> 8) & 255; }
+__device__ __forceinline__ int bv_pix(const BvRec& r) { return __float_as_int(r.d.y); }
+__device__ __forceinline__ int bv_mat(const BvRec& r) { return __float_as_int(r.d.z); }
 // one stored vertex: position, local wi, throughput, dVCM, dVC, primitive,
-// (len, nspec, material) and the camera pixel
+// (len, nspec), the camera pixel and the material
 __device__ __forceinline__ void store_vertex(float* s, int i, V3 pos, const Bsdf& b, V3 thr, float dvcm, float dvc,
                                              int prim, int len, int nspec, int pix) {
-  bvst3(s, i, BV_POS, pos);
-  bvst3(s, i, BV_WI, b.wi);
-  bvst3(s, i, BV_THR, thr);
-  bvf(s, i, BV_DVCM) = dvcm;
-  bvf(s, i, BV_DVC) = dvc;
-  bvi(s, i, BV_PRIM) = prim;
-  bvi(s, i, BV_PACK) = bv_pack(len, nspec, b.mat);
-  bvi(s, i, BV_PIX) = pix;
+  float4* r = reinterpret_cast<float4*>(s) + 4 * size_t(i);
+  r[0] = make_float4(pos.x, pos.y, pos.z, b.wi.x);
+  r[1] = make_float4(b.wi.y, b.wi.z, thr.x, thr.y);
+  r[2] = make_float4(thr.z, dvcm, dvc, __int_as_float(prim));
+  r[3] = make_float4(__int_as_float(len | (nspec << 8)), __int_as_float(pix), __int_as_float(b.mat), 0.f);
 }
-// the BSDF of stored vertex i (BSDF::init at its hit, bsdf.h:66-89)
-__device__ __forceinline__ Bsdf stored_bsdf(const DevScene& S, const float* s, int i, int pack) {
+// the BSDF of stored vertex v (BSDF::init at its hit, bsdf.h:66-89); the
+// primitive's records are read together, the sphere word only in a scene
+// that has a sphere
+struct PrimIn {
+  float4 r0, r1, cs;  // prim_rec's two words, prim_sph
+};
+__device__ __forceinline__ PrimIn prim_inputs(const DevScene& S, int has_sph, int prim) {
+  PrimIn g;
+  g.r0 = S.prim_rec[2 * static_cast<size_t>(prim)];
+  g.r1 = S.prim_rec[2 * static_cast<size_t>(prim) + 1];
+  g.cs = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (has_sph) g.cs = S.prim_sph[prim];
+  return g;
+}
+__device__ __forceinline__ Bsdf stored_bsdf(const PrimIn& g, const DMat* mats, const BvRec& v) {
   Bsdf b;
-  b.fr = frame_from_z(prim_normal(S, bvi(const_cast<float*>(s), i, BV_PRIM), bvld3(s, i, BV_POS)));
-  b.wi = bvld3(s, i, BV_WI);
-  bsdf_probs(b, bv_mat(pack), S.mats);
+  b.fr = frame_from_z(prim_normal(g.r0, g.r1, g.cs, bv_pos(v)));
+  b.wi = bv_wi(v);
+  bsdf_probs(b, bv_mat(v), mats);
   return b;
 }
 
@@ -234,6 +266,8 @@ struct BdptArgs {
   int ctl, maxlen, faithful;
   int overlap = 0;  // 1: the overlapped schedule (light splats into the step's sq, CV store, light-side connections)
   int untiled = 0;  // 1: camera paths in plain path order (a render redone with small pieces, BdptBuf)
+  int nmats = 0;    // entries of S.mats (material 0 is unused)
+  int has_sph = 0;  // the scene has a sphere: prim_sph is worth a load (else prim_rec's type word is 0 everywhere)
 };
 // First queue index of the camera pass's extension rays of step `slot`
 // (kCamSlot + bounce): overlapped, behind the light pass's rays of the same
@@ -284,10 +318,44 @@ __device__ __forceinline__ bool sq_fits(const BdptArgs& A, bool want, int si) {
 #define WR_TEST_SPLAT_W 1.f
 #endif
 
+// The material and light tables in LDS (the gen and vertex kernels' template
+// flag GT = false; GT = true reads the global tables; chosen by the host per
+// scene: bdpt_lds_tables): every BSDF
+// call reads its DMat, and a global read there is a round trip behind the
+// material index that the compiler repeats after each store (it cannot know
+// the table is not written).  A scene above either cap keeps the global
+// tables.  The choice is a template flag, not a run-time select, so that the
+// pointers' address space is known where they are used.
+constexpr int kLdsMats = 32, kLdsLights = 16;
+constexpr int kMatWords = sizeof(DMat) / 4, kLightWords = sizeof(DLight) / 4;
+constexpr int kLdsTabWords = kLdsMats * kMatWords + kLdsLights * kLightWords;  // 2.8 KB
+static_assert(sizeof(DMat) % 4 == 0 && sizeof(DLight) % 4 == 0, "tables are copied by words");
+// every thread of the block calls it, before any thread leaves the kernel
+__device__ __forceinline__ void tables_to_lds(const BdptArgs& A, float* tab) {
+  const float* gm = reinterpret_cast<const float*>(A.S.mats);
+  const float* gl = reinterpret_cast<const float*>(A.S.lights);
+  const int nm = min(A.nmats, kLdsMats) * kMatWords, nl = min(A.S.nlights, kLdsLights) * kLightWords;
+  for (int i = threadIdx.x; i < nm; i += blockDim.x) tab[i] = gm[i];
+  for (int i = threadIdx.x; i < nl; i += blockDim.x) tab[kLdsMats * kMatWords + i] = gl[i];
+  __syncthreads();
+}
+#define WR_BDPT_TABLES(A_)                                                         \
+  __shared__ float s_tab_[GT ? 1 : kLdsTabWords];                                  \
+  const DMat* mats = (A_).S.mats;                                                  \
+  const DLight* lights = (A_).S.lights;                                            \
+  if constexpr (!GT) {                                                             \
+    tables_to_lds(A_, s_tab_);                                                     \
+    mats = reinterpret_cast<const DMat*>(s_tab_);                                  \
+    lights = reinterpret_cast<const DLight*>(s_tab_ + kLdsMats * kMatWords);       \
+  }
+
 // generateLightSample (:267-311) + the first extension ray
+template <bool GT>
 __global__ void __launch_bounds__(kShadeBlock) WR_NO_PK_FP32 k_light_gen(BdptGroup G_) {
   const BdptArgs& A = G_.a[blockIdx.y];
   const BdptBuf& B = A.B;
+  WR_BDPT_TABLES(A)
+  (void)mats;
   // (queues use the stride B.qs)
   const float lpp = 1.f / static_cast<float>(A.S.nlights);
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < A.n; p += gridDim.x * blockDim.x) {
@@ -295,7 +363,7 @@ __global__ void __launch_bounds__(kShadeBlock) WR_NO_PK_FP32 k_light_gen(BdptGro
     // the camera path of the same global index, :130, :222-229)
     Rng rng{stream_key(A.seed, A.iter, 0, static_cast<uint32_t>(A.base + p)), 0};
     const int id = min(static_cast<int>(rng.f() * static_cast<float>(A.S.nlights)), A.S.nlights - 1);
-    const DLight L = A.S.lights[id];
+    const DLight L = lights[id];
     V3 pos, dir, rad;
     float epdf = 0.f, dpdf = 0.f;
     for (int tries = 0; tries < 64; ++tries) {
@@ -310,11 +378,10 @@ __global__ void __launch_bounds__(kShadeBlock) WR_NO_PK_FP32 k_light_gen(BdptGro
     epdf *= lpp;
     dpdf *= lpp;
     thr = div_plain(thr, epdf);
-    bqst3(B.ls, p, BQ_THR, thr);
-    bqf(B.ls, p, BQ_DVCM) = dpdf / epdf;
-    bqf(B.ls, p, BQ_DVC) = 1.f / epdf;  // AreaLight::isDelta() == 0
-    bqu(B.ls, p, BQ_CTR) = rng.ctr;
-    bqi(B.ls, p, BQ_PACK) = bq_pack(1, 0, 0);  // pathLength 1, no specular vertex, no stored vertex
+    // dVC = 1 / epdf: AreaLight::isDelta() == 0; pathLength 1, no specular
+    // vertex, no stored vertex (a light path has no pixel: the last word is 0)
+    bq_store_a(B.ls, p, bq_half_a(thr, dpdf / epdf));
+    bq_store_b(B.ls, p, bq_half_b(1.f / epdf, rng.ctr, bq_pack(1, 0, 0), 0));
     B.lvc[p] = kLightAlive;  // no stored vertex, the first ray queued
     // Ray(origin + dir * EPS, dir) (:79-80)
     st3(B.q_o[0], B.qs, p, pos + dir * WR_EPS);
@@ -325,16 +392,16 @@ __global__ void __launch_bounds__(kShadeBlock) WR_NO_PK_FP32 k_light_gen(BdptGro
 }
 
 // sampleScattering (:370-416).  Returns false when the subpath ends.
-__device__ __forceinline__ bool sample_scatter(const DevScene& S, Rng& rng, const Bsdf& b, V3 hit, V3& o, V3& dir,
+__device__ __forceinline__ bool sample_scatter(const DMat* mats, Rng& rng, const Bsdf& b, V3 hit, V3& o, V3& dir,
                                                V3& thr, float& dvcm, float& dvc, int& nspec) {
   float dpdf = 0.f, cos_wo = 0.f;
   int type;
   V3 wo = dir;
-  const V3 f = bsdf_sample(b, S.mats, rng.v(), &wo, &dpdf, &cos_wo, &type);
+  const V3 f = bsdf_sample(b, mats, rng.v(), &wo, &dpdf, &cos_wo, &type);
   if (black(f)) return false;
   dir = wo;
   float rpdf = dpdf;
-  if ((type & T_SPEC) == 0) rpdf = bsdf_pdf(b, S.mats, dir, true);
+  if ((type & T_SPEC) == 0) rpdf = bsdf_pdf(b, mats, dir, true);
   const float cp = b.cont;
   if (rng.f() > cp) return false;
   dpdf *= cp;
@@ -359,26 +426,25 @@ __device__ __forceinline__ bool sample_scatter(const DevScene& S, Rng& rng, cons
 // ray is traced: faithful); sdir / stgt / sval then hold the ray and the value
 // splatted if unoccluded.  One function for both sides of the overlapped
 // schedule, so a pair's floats do not depend on which vertex came second.
-__device__ __forceinline__ bool connect_pair(const BdptArgs& A, const Bsdf& b, V3 hp, V3 cthr, float cdvcm, float cdvc,
-                                             int cnspec, int len, int slot, int llen, V3& sdir, V3& stgt, V3& sval,
-                                             bool& counted) {
-  const BdptBuf& B = A.B;
+__device__ __forceinline__ bool connect_pair(const BdptArgs& A, const DMat* mats, const Bsdf& b, V3 hp, V3 cthr,
+                                             float cdvcm, float cdvc, int cnspec, int len, const BvRec& lv, int llen,
+                                             V3& sdir, V3& stgt, V3& sval, bool& counted) {
   const DevScene& S = A.S;
   bool shoot = false;
-  const V3 lpos = bvld3(B.vs, slot, BV_POS);
+  const PrimIn lg = prim_inputs(S, A.has_sph, bv_prim(lv));  // (asked for now, used once the camera side's f is known)
+  const V3 lpos = bv_pos(lv);
   V3 dir = lpos - hp;
   const float d2 = sqr_len(dir);
   const float dist = sqrtf(d2);
   dir = div_guarded(dir, dist);
   float cos_c = 0.f, cdp, crp;
-  const V3 cf = bsdf_f(b, S.mats, dir, &cos_c, &cdp, &crp);
+  const V3 cf = bsdf_f(b, mats, dir, &cos_c, &cdp, &crp);
   if (!black(cf)) {
     cdp *= b.cont;
     crp *= b.cont;
-    const int lpk = bvi(B.vs, slot, BV_PACK);
-    const Bsdf lb = stored_bsdf(S, B.vs, slot, lpk);
+    const Bsdf lb = stored_bsdf(lg, mats, lv);
     float cos_l = 0.f, ldp, lrp;
-    const V3 lf = bsdf_f(lb, S.mats, -dir, &cos_l, &ldp, &lrp);
+    const V3 lf = bsdf_f(lb, mats, -dir, &cos_l, &ldp, &lrp);
     if (!black(lf)) {
       ldp *= lb.cont;
       lrp *= lb.cont;
@@ -388,7 +454,7 @@ __device__ __forceinline__ bool connect_pair(const BdptArgs& A, const Bsdf& b, V
         const float ldpa = ldp * fabsf(cos_c) / (dist * dist);
         const V3 res = mul(cf, lf) * G;
         if (!black(res)) {
-          const float wl = cdpa * (bvf(B.vs, slot, BV_DVCM) + lrp * bvf(B.vs, slot, BV_DVC));
+          const float wl = cdpa * (bv_dvcm(lv) + lrp * bv_dvc(lv));
           const float wc = ldpa * (cdvcm + crp * cdvc);
           const float w = WR_TEST_CONN_W / (wl + 1.f + wc);
           const bool counts = len_ok(A.ctl, llen + 1 + len);
@@ -399,8 +465,8 @@ __device__ __forceinline__ bool connect_pair(const BdptArgs& A, const Bsdf& b, V
             stgt = hp + dir * dist;
             if (counts) {
               const float wlen = 1.f / (static_cast<float>(llen) + 1.f + static_cast<float>(len) -
-                                        static_cast<float>(bv_nspec(lpk)) - static_cast<float>(cnspec));
-              const V3 lthr = bvld3(B.vs, slot, BV_THR);
+                                        static_cast<float>(bv_nspec(lv)) - static_cast<float>(cnspec));
+              const V3 lthr = bv_thr(lv);
               sval = mul(mul(cthr, lthr), res * w) * wlen;
             }
           }
@@ -437,27 +503,62 @@ __device__ __forceinline__ void queue_connection(const BdptArgs& A, int qslot, b
   }
 }
 
+// A vertex's inputs, read in two stages instead of one load behind another.
+// Stage A (the callers): the ray's queue columns, all together.  Stage B
+// (vertex_inputs): everything whose address follows from the path and the
+// primitive -- the primitive's records, the path's state record and the other
+// pass's vertex count -- issued as one straight-line block before any of it
+// is used.  A lane without work (no queue entry, a miss, a pending hard ray)
+// reads record 0 and drops it, so no branch guards a load.
+struct VtxIn {
+  int p, prim;  // p = -1: the lane has no queue entry
+  float t;
+  V3 o, d;
+  PrimIn g;
+  BqRec st;
+  int oc;  // light vertex: cvc[p] (overlapped schedule), camera vertex: lvc[p]
+};
+// p: a valid local path for every lane (the callers clamp the queue index);
+// on: the lane has a queue entry
+template <bool CAMERA>
+__device__ __forceinline__ VtxIn vertex_inputs(const BdptArgs& A, bool on, int p, int prim, float t, V3 o, V3 d) {
+  const BdptBuf& B = A.B;
+  VtxIn v;
+  v.g = prim_inputs(A.S, A.has_sph, max(prim, 0));
+  v.st = bq_load(CAMERA ? B.cs : B.ls, p);
+  v.oc = CAMERA ? B.lvc[p] : (A.overlap ? B.cvc[p] : 0);
+  v.p = on ? p : -1;
+  v.prim = on ? prim : -1;
+  v.t = t;
+  v.o = o;
+  v.d = d;
+  return v;
+}
+
 // One light-subpath vertex (:77-128): path p's ray (o, d) hit prim at t
 // (prim < 0: a miss, or a pending hard ray -- nothing to do).  Every lane of
 // the wave calls it (queue appends).  oslot: the step whose queue gets the
 // extension ray -- slot + 1, or slot + 2 for a deferred vertex (k_late_light).
-__device__ __forceinline__ void light_vertex(const BdptArgs& A, int p, int prim, float t, V3 o, V3 d, int oslot) {
+__device__ __forceinline__ void light_vertex(const BdptArgs& A, const DMat* mats, const VtxIn& in, int oslot) {
   const BdptBuf& B = A.B;
   const DevScene& S = A.S;
   const int P = B.P, nxt = oslot & 1;  // P: buffer stride (local paths)
+  const int p = in.p, prim = in.prim;
+  const float t = in.t;
+  const V3 d = in.d;
   bool ext = false, splat = false;
   V3 e_o, e_d, s_o, s_d, s_val;
   int s_pix = -1;
   int lconn = 0, lslot = -1, llen = 0;  // overlapped: the stored vertex's slot, camera vertices to connect
+  const int pk = __float_as_int(in.st.b.z);
   if (prim >= 0) {
-    const Hit h = rebuild_hit(S, prim, t, o, d);
+    const Hit h = rebuild_hit(S, prim, t, in.o, d, in.g.r0, in.g.r1, in.g.cs);
     Bsdf b;
-    bsdf_init(b, -d, h.n, h.mat, S.mats);
+    bsdf_init(b, -d, h.n, h.mat, mats);
     if (b.mat != 0) {
-      float dvcm = bqf(B.ls, p, BQ_DVCM), dvc = bqf(B.ls, p, BQ_DVC);
-      const int pk = bqi(B.ls, p, BQ_PACK);
+      float dvcm = in.st.a.w, dvc = in.st.b.x;
       int len = bq_len(pk), nspec = bq_nspec(pk), nstored = bq_count(pk);
-      V3 thr = bqld3(B.ls, p, BQ_THR);
+      V3 thr = v3(in.st.a.x, in.st.a.y, in.st.a.z);
       dvcm *= (t * t);  // pathLength > 1 || isFiniteLight: always for area lights (:94-97)
       dvcm /= fabsf(b.wi.z);
       dvc /= fabsf(b.wi.z);
@@ -473,7 +574,7 @@ __device__ __forceinline__ void light_vertex(const BdptArgs& A, int p, int prim,
         if (A.overlap && slot >= 0) {  // the camera vertices stored at earlier steps (lengths < len)
           lslot = slot;
           llen = len;
-          lconn = B.cvc[p];
+          lconn = in.oc;
         }
         if (len_ok(A.ctl, len + 1)) {  // connectToCamera (:105-120, :313-368)
           const DCam& cam = S.cam;
@@ -485,7 +586,7 @@ __device__ __forceinline__ void light_vertex(const BdptArgs& A, int p, int prim,
               const float dist = sqrtf(d2);
               dtc = div_guarded(dtc, dist);
               float cos_to = 0.f, dp, rp;
-              const V3 f = bsdf_f(b, S.mats, dtc, &cos_to, &dp, &rp);
+              const V3 f = bsdf_f(b, mats, dtc, &cos_to, &dp, &rp);
               if (!black(f)) {
                 rp *= b.cont;
                 const float cos_at = dot(-dtc, cam.fwd);
@@ -520,28 +621,36 @@ __device__ __forceinline__ void light_vertex(const BdptArgs& A, int p, int prim,
         }
       }
       if (!(len + 2 > A.maxlen)) {  // (:123-127)
-        Rng rng{stream_key(A.seed, A.iter, 0, static_cast<uint32_t>(A.base + p)), bqu(B.ls, p, BQ_CTR)};
+        Rng rng{stream_key(A.seed, A.iter, 0, static_cast<uint32_t>(A.base + p)), __float_as_uint(in.st.b.y)};
         V3 lo{}, ld{};  // sampleScattering's origin and direction (outputs only)
-        if (sample_scatter(S, rng, b, h.p, lo, ld, thr, dvcm, dvc, nspec)) {
+        if (sample_scatter(mats, rng, b, h.p, lo, ld, thr, dvcm, dvc, nspec)) {
           ext = true;
           ++len;
           e_o = lo + ld * WR_EPS;
           e_d = normalize(ld);
-          bqst3(B.ls, p, BQ_THR, thr);
-          bqf(B.ls, p, BQ_DVCM) = dvcm;
-          bqf(B.ls, p, BQ_DVC) = dvc;
         }
-        bqu(B.ls, p, BQ_CTR) = rng.ctr;
+        // The record goes back as whole 16-byte halves.  A scattered path: all
+        // of it -- thr, dVCM, dVC, len / nspec of the next vertex.  Otherwise
+        // only the half with the counter and the stored vertices (dVC and the
+        // last word as they were read).
+        if (ext) {
+          bq_store_a(B.ls, p, bq_half_a(thr, dvcm));
+          bq_store_b(B.ls, p, bq_half_b(dvc, rng.ctr, bq_pack(len, nspec, nstored), __float_as_int(in.st.b.w)));
+        } else {
+          bq_store_b(B.ls, p, bq_half_b(in.st.b.x, rng.ctr, bq_pack(len, nspec, nstored), __float_as_int(in.st.b.w)));
+        }
+      } else if (nstored != bq_count(pk)) {
+        bq_store_b(B.ls, p, make_float4(in.st.b.x, in.st.b.y, __int_as_float(bq_pack(len, nspec, nstored)), in.st.b.w));
       }
-      // len / nspec of the next vertex (when it scatters), the stored vertices
-      if (ext || nstored != bq_count(pk)) bqi(B.ls, p, BQ_PACK) = bq_pack(len, nspec, nstored);
       const int lv = nstored | (ext ? kLightAlive : 0);
       if (lv != (bq_count(pk) | kLightAlive)) B.lvc[p] = static_cast<uint8_t>(lv);
     } else {  // an invalid BSDF ends the subpath (:86-88)
-      B.lvc[p] &= static_cast<uint8_t>(~kLightAlive);
+      B.lvc[p] = static_cast<uint8_t>(bq_count(pk));
     }
   } else if (p >= 0) {  // a miss ends the subpath (:81-82)
-    B.lvc[p] &= static_cast<uint8_t>(~kLightAlive);
+    // (lvc's low bits are always the state record's stored-vertex count, so
+    // clearing kLightAlive needs no read of the byte)
+    B.lvc[p] = static_cast<uint8_t>(bq_count(pk));
   }
   const int ei = wave_append(&A.sc->ext[oslot], ext);
   if (ext) {
@@ -566,22 +675,24 @@ __device__ __forceinline__ void light_vertex(const BdptArgs& A, int p, int prim,
   // overlapped schedule: this light vertex connects to the path's camera
   // vertices stored at earlier steps (:219-257 reached from the camera side)
   if (A.overlap && __ballot(lconn > 0)) {
+    BvRec lv{};  // this light vertex as stored (lconn > 0: it has a record)
+    if (lconn > 0) lv = bv_load(B.vs, lslot);
     for (int j = 0; __ballot(j < lconn); ++j) {
       bool shoot = false, counted = false;
       int pix = -1;
       V3 hp{}, sdir{}, stgt{}, sval{};
       const int cs = j < lconn ? cv_slot(B, j, p) : -1;
       if (cs >= 0) {
-        const int cpk = bvi(B.cv, cs, BV_PACK);
-        const int clen = bv_len(cpk);
+        const BvRec cv = bv_load(B.cv, cs);
+        const int clen = bv_len(cv);
         if (llen + 1 + clen > A.maxlen) {
           lconn = j;  // camera vertices are stored by increasing length
         } else {
-          const Bsdf cb = stored_bsdf(S, B.cv, cs, cpk);
-          hp = bvld3(B.cv, cs, BV_POS);
-          pix = bvi(B.cv, cs, BV_PIX);
-          shoot = connect_pair(A, cb, hp, bvld3(B.cv, cs, BV_THR), bvf(B.cv, cs, BV_DVCM), bvf(B.cv, cs, BV_DVC),
-                               bv_nspec(cpk), clen, lslot, llen, sdir, stgt, sval, counted);
+          const Bsdf cb = stored_bsdf(prim_inputs(S, A.has_sph, bv_prim(cv)), mats, cv);
+          hp = bv_pos(cv);
+          pix = bv_pix(cv);
+          shoot = connect_pair(A, mats, cb, hp, bv_thr(cv), bv_dvcm(cv), bv_dvc(cv), bv_nspec(cv), clen, lv, llen, sdir,
+                               stgt, sval, counted);
         }
       }
       queue_connection(A, sslot, shoot, counted, p, pix, hp, sdir, stgt, sval);
@@ -590,16 +701,18 @@ __device__ __forceinline__ void light_vertex(const BdptArgs& A, int p, int prim,
 }
 
 template <bool CAMERA>
-__device__ __forceinline__ void late_vertex_body(const BdptArgs& A, const LateList& LL, const int* cnt, int slot,
-                                                 int bid, int nblk);
+__device__ __forceinline__ void late_vertex_body(const BdptArgs& A, const DMat* mats, const DLight* lights,
+                                                 const LateList& LL, const int* cnt, int slot, int bid, int nblk);
 // Blocks [0, gridDim.x - nlate) shade this step's vertices, the last nlate
 // blocks the previous step's deferred ones (late_vertex_body).
+template <bool GT>
 __global__ void __launch_bounds__(kShadeBlock) WR_SHADE_OCC k_light_shade(BdptGroup G_, int slot, LateArgs L,
                                                                          int nlate) {
   const BdptArgs& A = G_.a[blockIdx.y];
+  WR_BDPT_TABLES(A)
   const int nmain = static_cast<int>(gridDim.x) - nlate;
   if (static_cast<int>(blockIdx.x) >= nmain) {
-    late_vertex_body<false>(A, L.l[blockIdx.y], L.n[blockIdx.y], slot, blockIdx.x - nmain, nlate);
+    late_vertex_body<false>(A, mats, lights, L.l[blockIdx.y], L.n[blockIdx.y], slot, blockIdx.x - nmain, nlate);
     return;
   }
   const BdptBuf& B = A.B;
@@ -609,26 +722,18 @@ __global__ void __launch_bounds__(kShadeBlock) WR_SHADE_OCC k_light_shade(BdptGr
   const int gstride = nmain * blockDim.x;
   const int nround = (n + gstride - 1) / gstride * gstride;  // whole waves reach the appends
   for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < nround; j += gstride) {
-    int p = -1, prim = -1;
-    float t = 0.f;
-    V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 0.f);
-    if (j < n) {
-      p = B.q_path[cur][j];
-      prim = B.q_prim[cur][j];
+    // stage A: the entry's columns, all at once (a lane past the end reads the
+    // last entry; n > 0 here)
+    const int e = min(j, n - 1);
+    const int p = B.q_path[cur][e], prim = B.q_prim[cur][e];
+    const float t = B.q_t[cur][e];
+    const V3 o = ld3(B.q_o[cur], B.qs, e), d = ld3(B.q_d[cur], B.qs, e);
 #ifdef WR_DEBUG_PATH
-      if (A.base + p == WR_DEBUG_PATH && A.iter == WR_DEBUG_ITER) {
-        const V3 o = ld3(B.q_o[cur], B.qs, j), d = ld3(B.q_d[cur], B.qs, j);
-        printf("[dbg gpu] light step %d ray o %a %a %a d %a %a %a prim %d t %a\n", slot, o.x, o.y, o.z, d.x, d.y, d.z, prim,
-               B.q_t[cur][j]);
-      }
+    if (j < n && A.base + p == WR_DEBUG_PATH && A.iter == WR_DEBUG_ITER)
+      printf("[dbg gpu] light step %d ray o %a %a %a d %a %a %a prim %d t %a\n", slot, o.x, o.y, o.z, d.x, d.y, d.z, prim,
+             t);
 #endif
-      if (prim >= 0) {
-        t = B.q_t[cur][j];
-        o = ld3(B.q_o[cur], B.qs, j);
-        d = ld3(B.q_d[cur], B.qs, j);
-      }
-    }
-    light_vertex(A, p, prim, t, o, d, slot + 1);
+    light_vertex(A, mats, vertex_inputs<false>(A, j < n, p, prim, t, o, d), slot + 1);
   }
 }
 
@@ -675,12 +780,9 @@ __device__ __forceinline__ int camera_gen_one(const BdptArgs& A, int s, int ebas
     psu(B.cs, l, PS_CTR) = rng.ctr;
     psi(B.cs, l, PS_PIX) = pix;  // (VertexCM's camera gen sets PS_DVM after this)
   } else {
-    bqst3(B.cs, l, BQ_THR, v3(1.f, 1.f, 1.f));
-    bqf(B.cs, l, BQ_DVCM) = static_cast<float>(A.P) / i2sa;  // lightPathNum / cameraPdf
-    bqf(B.cs, l, BQ_DVC) = 0.f;
-    bqu(B.cs, l, BQ_CTR) = rng.ctr;
-    bqi(B.cs, l, BQ_PACK) = bq_pack(1, 0, 0);  // no camera vertex stored yet
-    bqi(B.cs, l, BQ_PIX) = pix;
+    // dVCM = lightPathNum / cameraPdf, dVC = 0; no camera vertex stored yet
+    bq_store_a(B.cs, l, bq_half_a(v3(1.f, 1.f, 1.f), static_cast<float>(A.P) / i2sa));
+    bq_store_b(B.cs, l, bq_half_b(0.f, rng.ctr, bq_pack(1, 0, 0), pix));
     B.cvc[l] = 0;
   }
   const int e = ebase + s;  // overlapped: behind the light pass's first rays (cam_ext_base)
@@ -704,33 +806,36 @@ __global__ void __launch_bounds__(kShadeBlock) WR_NO_PK_FP32 k_camera_gen(BdptGr
 // vertex (k_late_camera).
 // ebase: the queue index of the camera pass's first extension ray of step
 // oslot (cam_ext_base, read once by the caller)
-__device__ __forceinline__ void camera_vertex(const BdptArgs& A, int p, int prim, float t, V3 o, V3 d, int oslot,
-                                              int ebase = 0) {
+__device__ __forceinline__ void camera_vertex(const BdptArgs& A, const DMat* mats, const DLight* lights,
+                                              const VtxIn& in, int oslot, int ebase = 0) {
   const BdptBuf& B = A.B;
   const DevScene& S = A.S;
   const int P = B.P, nxt = oslot & 1, cap = B.cap_sq;  // P: buffer stride
+  const int p = in.p, prim = in.prim;
+  const float t = in.t;
+  const V3 d = in.d;
   const float lpp = 1.f / static_cast<float>(S.nlights);
   const BdptBuf::Sq& Q = B.sq[oslot & 1];  // rays traced at step oslot
   const BdptBuf::Di& D = B.di[oslot & 1];
-  bool live = false, ext = false, conn_phase = false, nee = false, dib = false;
+  bool ext = false, conn_phase = false, nee = false, dib = false;
   int pix = -1, nv = 0, len = 0, nspec = 0, cnspec = 0, pk = 0, ncv = 0;  // ncv: stored camera vertices
   V3 hp{}, thr{}, cthr{}, e_o{}, e_d{}, nee_tgt{}, nee_d{}, dib_o{}, dib_d{};
   float dvcm = 0.f, dvc = 0.f, cdvcm = 0.f, cdvc = 0.f;
   Bsdf b;
   b.mat = 0;
   if (prim >= 0) {
-    const Hit h = rebuild_hit(S, prim, t, o, d);
-    bsdf_init(b, -d, h.n, h.mat, S.mats);
+    const Hit h = rebuild_hit(S, prim, t, in.o, d, in.g.r0, in.g.r1, in.g.cs);
+    bsdf_init(b, -d, h.n, h.mat, mats);
     if (b.mat != 0) {
       hp = h.p;
-      pix = bqi(B.cs, p, BQ_PIX);
-      dvcm = bqf(B.cs, p, BQ_DVCM);
-      dvc = bqf(B.cs, p, BQ_DVC);
-      pk = bqi(B.cs, p, BQ_PACK);
+      pix = __float_as_int(in.st.b.w);
+      dvcm = in.st.a.w;
+      dvc = in.st.b.x;
+      pk = __float_as_int(in.st.b.z);
       len = bq_len(pk);
       nspec = bq_nspec(pk);
       ncv = bq_count(pk);
-      thr = bqld3(B.cs, p, BQ_THR);
+      thr = v3(in.st.a.x, in.st.a.y, in.st.a.z);
       dvcm *= (t * t);  // (:180-182)
       dvcm /= fabsf(b.wi.z);
       dvc /= fabsf(b.wi.z);
@@ -742,7 +847,7 @@ __device__ __forceinline__ void camera_vertex(const BdptArgs& A, int p, int prim
       cnspec = nspec;
       if (h.mat < 0) {  // hit an emitter (:184-199)
         if (len_ok(A.ctl, len)) {
-          const DLight L = S.lights[-h.mat - 1];
+          const DLight L = lights[-h.mat - 1];
           float dpa, ep;
           V3 r = light_radiance(L, d, &dpa, &ep);
           if (!black(r)) {
@@ -756,12 +861,11 @@ __device__ __forceinline__ void camera_vertex(const BdptArgs& A, int p, int prim
           }
         }
       } else if (len < A.maxlen) {
-        live = true;
-        Rng rng{stream_key(A.seed, A.iter, 1, static_cast<uint32_t>(A.base + p)), bqu(B.cs, p, BQ_CTR)};
+        Rng rng{stream_key(A.seed, A.iter, 1, static_cast<uint32_t>(A.base + p)), __float_as_uint(in.st.b.y)};
         if (!b.delta && len_ok(A.ctl, len + 1)) {  // getDirectIllumination (:205-217, :484-608)
           const float wlen = 1.f / (static_cast<float>(len) + 1.f - static_cast<float>(nspec));
           const int lid = min(static_cast<int>(rng.f() * static_cast<float>(S.nlights)), S.nlights - 1);
-          const DLight L = S.lights[lid];
+          const DLight L = lights[lid];
           V3 dtl;
           float dist = 0.f, dpdf = 0.f, epdf = 0.f, cal = 0.f;
           const V3 illu = light_illuminance(L, hp, rng.v(), &dtl, &dist, &dpdf, &epdf, &cal);
@@ -770,7 +874,7 @@ __device__ __forceinline__ void camera_vertex(const BdptArgs& A, int p, int prim
           float nee_w = 0.f;
           if (!black(illu) && dpdf > 0) {
             float cos_to = 0.f, bdp, brp;
-            const V3 bf = bsdf_f(b, S.mats, dtl, &cos_to, &bdp, &brp);
+            const V3 bf = bsdf_f(b, mats, dtl, &cos_to, &bdp, &brp);
             if (!black(bf)) {
               bdp *= b.cont;
               brp *= b.cont;
@@ -790,7 +894,7 @@ __device__ __forceinline__ void camera_vertex(const BdptArgs& A, int p, int prim
           V3 dtl2 = dtl;
           float dpdf2 = dpdf, cos_s = 0.f;
           int type;
-          const V3 bf2 = bsdf_sample(b, S.mats, rng.v(), &dtl2, &dpdf2, &cos_s, &type);
+          const V3 bf2 = bsdf_sample(b, mats, rng.v(), &dtl2, &dpdf2, &cos_s, &type);
           if (!black(bf2) && dpdf2 > 0) {
             float w = 1.f;
             V3 illu2 = illu;
@@ -815,20 +919,17 @@ __device__ __forceinline__ void camera_vertex(const BdptArgs& A, int p, int prim
           // nor the BSDF ray the contribution is exactly zero (:533-607)
           const int nrays = (nee ? 1 : 0) + (dib ? 1 : 0);
           if (nrays > 0) {
-            dri(D.r, p, DR_FLAGS) = flags;
-            drst3(D.r, p, DR_NEE, nee_val);
-            drf(D.r, p, DR_NEEW) = nee_w;
-            drst3(D.r, p, DR_BSDF, bsdf_val);
-            drst3(D.r, p, DR_THR, thr);
-            drf(D.r, p, DR_WLEN) = wlen;
-            dri(D.r, p, DR_LIGHT) = lid;
-            dri(D.r, p, DR_PIX) = pix;
-            dri(D.r, p, DR_STATE) = nrays;
+            // (the whole record, as four 16-byte stores; word 15 is unused)
+            float4* r = reinterpret_cast<float4*>(D.r) + 4 * size_t(p);
+            r[0] = make_float4(nee_val.x, nee_val.y, nee_val.z, nee_w);
+            r[1] = make_float4(bsdf_val.x, bsdf_val.y, bsdf_val.z, thr.x);
+            r[2] = make_float4(thr.y, thr.z, wlen, __int_as_float(flags));
+            r[3] = make_float4(__int_as_float(lid), __int_as_float(pix), __int_as_float(nrays), 0.f);
           }
         }
         if (!b.delta) {
           conn_phase = true;
-          const int lv = B.lvc[p];
+          const int lv = in.oc;
           nv = lv & ~kLightAlive;
           // overlapped schedule: a vertex a later light vertex may still meet
           // (len < l, l + 1 + len <= maxlen) is kept for that light vertex --
@@ -846,14 +947,23 @@ __device__ __forceinline__ void camera_vertex(const BdptArgs& A, int p, int prim
           }
         }
         V3 so{}, sd{};  // sampleScattering's origin and direction (outputs only)
-        if (sample_scatter(S, rng, b, hp, so, sd, thr, dvcm, dvc, nspec)) {
+        if (sample_scatter(mats, rng, b, hp, so, sd, thr, dvcm, dvc, nspec)) {
           ext = true;
           e_o = so + sd * WR_EPS;
           e_d = normalize(sd);
         }
-        bqu(B.cs, p, BQ_CTR) = rng.ctr;
-        // the state for the NEXT vertex is committed below; the connections
-        // use the values of THIS vertex (cthr, cdvcm, cdvc, cnspec)
+        // Commit the state for the NEXT vertex (:259-260 and the loop
+        // increment) as whole 16-byte halves: all of the record when the path
+        // scattered, else the half with the counter and the stored vertices.
+        // The connections below use the values of THIS vertex (cthr, cdvcm,
+        // cdvc, cnspec).
+        if (ext) {
+          bq_store_a(B.cs, p, bq_half_a(thr, dvcm));
+          bq_store_b(B.cs, p, bq_half_b(dvc, rng.ctr, bq_pack(len + 1, nspec, ncv), pix));
+        } else {
+          bq_store_b(B.cs, p, bq_half_b(in.st.b.x, rng.ctr, bq_pack(len, nspec, ncv), pix));
+        }
+        if (ncv != bq_count(pk)) B.cvc[p] = static_cast<uint8_t>(ncv);
       }
     }
   }
@@ -884,26 +994,16 @@ __device__ __forceinline__ void camera_vertex(const BdptArgs& A, int p, int prim
       V3 sdir{}, stgt{}, sval{};
       const int slot = conn_phase && k < nv ? lv_slot(B, k, p) : -1;
       if (slot >= 0) {
-        const int llen = bv_len(bvi(B.vs, slot, BV_PACK));
+        const BvRec lv = bv_load(B.vs, slot);
+        const int llen = bv_len(lv);
         if (llen + 1 + len > A.maxlen) {
           nv = k;  // break (:237-239)
         } else {
-          shoot = connect_pair(A, b, hp, cthr, cdvcm, cdvc, cnspec, len, slot, llen, sdir, stgt, sval, counted);
+          shoot = connect_pair(A, mats, b, hp, cthr, cdvcm, cdvc, cnspec, len, lv, llen, sdir, stgt, sval, counted);
         }
       }
       queue_connection(A, oslot, shoot, counted, p, pix, hp, sdir, stgt, sval);
     }
-  }
-  if (live) {  // commit scattered state (:259-260) and the loop increment
-    if (ext) {
-      bqst3(B.cs, p, BQ_THR, thr);
-      bqf(B.cs, p, BQ_DVCM) = dvcm;
-      bqf(B.cs, p, BQ_DVC) = dvc;
-      bqi(B.cs, p, BQ_PACK) = bq_pack(len + 1, nspec, ncv);
-    } else if (ncv != bq_count(pk)) {
-      bqi(B.cs, p, BQ_PACK) = bq_pack(len, nspec, ncv);
-    }
-    if (ncv != bq_count(pk)) B.cvc[p] = static_cast<uint8_t>(ncv);
   }
   const int ei = wave_append(&A.sc->ext[oslot], ext) + ebase;
   if (ext) {
@@ -913,7 +1013,8 @@ __device__ __forceinline__ void camera_vertex(const BdptArgs& A, int p, int prim
   }
 }
 
-__device__ __forceinline__ void camera_shade_body(const BdptArgs& A, int slot, int bid, int nblk) {
+__device__ __forceinline__ void camera_shade_body(const BdptArgs& A, const DMat* mats, const DLight* lights, int slot,
+                                                  int bid, int nblk) {
   const BdptBuf& B = A.B;
   const int cur = slot & 1;
   const int n = A.sc->ext[slot], e0 = cam_ext_base(A, slot), eb = cam_ext_base(A, slot + 1);
@@ -921,20 +1022,13 @@ __device__ __forceinline__ void camera_shade_body(const BdptArgs& A, int slot, i
   const int gstride = nblk * blockDim.x;
   const int nround = (n + gstride - 1) / gstride * gstride;
   for (int j = bid * blockDim.x + threadIdx.x; j < nround; j += gstride) {
-    int p = -1, prim = -1;
-    float t = 0.f;
-    V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 0.f);
-    if (j < n) {
-      const int e = e0 + j;
-      p = B.q_path[cur][e];
-      prim = B.q_prim[cur][e];
-      if (prim >= 0) {
-        t = B.q_t[cur][e];
-        o = ld3(B.q_o[cur], B.qs, e);
-        d = ld3(B.q_d[cur], B.qs, e);
-      }
-    }
-    camera_vertex(A, p, prim, t, o, d, slot + 1, eb);
+    // stage A: the entry's columns, all at once (a lane past the end reads the
+    // last entry; n > 0 here)
+    const int e = e0 + min(j, n - 1);
+    const int p = B.q_path[cur][e], prim = B.q_prim[cur][e];
+    const float t = B.q_t[cur][e];
+    const V3 o = ld3(B.q_o[cur], B.qs, e), d = ld3(B.q_d[cur], B.qs, e);
+    camera_vertex(A, mats, lights, vertex_inputs<true>(A, j < n, p, prim, t, o, d), slot + 1, eb);
   }
 }
 
@@ -946,26 +1040,21 @@ __device__ __forceinline__ void camera_shade_body(const BdptArgs& A, int slot, i
 // connections (:130, :222-229) and every path keeps its own state, counters
 // and random numbers, so the film is the one of the undeferred render.
 template <bool CAMERA>
-__device__ __forceinline__ void late_vertex_body(const BdptArgs& A, const LateList& LL, const int* cnt, int slot,
-                                                 int bid, int nblk) {
+__device__ __forceinline__ void late_vertex_body(const BdptArgs& A, const DMat* mats, const DLight* lights,
+                                                 const LateList& LL, const int* cnt, int slot, int bid, int nblk) {
   const int half = LL.cap >> 1;
   const int nt = min(cnt[0], half), n = nt + min(cnt[1], half);
   const int gstride = nblk * blockDim.x;
   const int nround = (n + gstride - 1) / gstride * gstride;
   for (int j = bid * blockDim.x + threadIdx.x; j < nround; j += gstride) {
-    int p = -1, prim = -1;
-    float t = 0.f;
-    V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 0.f);
-    if (j < n) {
-      const int i = j < nt ? j : half + (j - nt);
-      p = LL.pth[i];
-      prim = LL.prim[i];
-      t = LL.t[i];
-      o = ld3(LL.o3, LL.cap, i);
-      d = ld3(LL.d3, LL.cap, i);
-    }
-    if (CAMERA) camera_vertex(A, p, prim, t, o, d, slot + 1);
-    else light_vertex(A, p, prim, t, o, d, slot + 1);
+    // (a lane past the end reads the last record; n > 0 here)
+    const int jc = min(j, n - 1), i = jc < nt ? jc : half + (jc - nt);
+    const int p = LL.pth[i], prim = LL.prim[i];
+    const float t = LL.t[i];
+    const V3 o = ld3(LL.o3, LL.cap, i), d = ld3(LL.d3, LL.cap, i);
+    const VtxIn in = vertex_inputs<CAMERA>(A, j < n, p, prim, t, o, d);
+    if (CAMERA) camera_vertex(A, mats, lights, in, slot + 1);
+    else light_vertex(A, mats, in, slot + 1);
   }
 }
 
@@ -1051,11 +1140,16 @@ __device__ __forceinline__ void sq_resolve_body(const BdptArgs& A, int slot, int
 // different queue / DI buffers.  The last step has no vertices (shade = 0).
 // ... blocks [0, nres) resolve, then this step's vertices, then (the last
 // nlate blocks) the previous step's deferred vertices.
+template <bool GT>
 __global__ void __launch_bounds__(kShadeBlock) WR_SHADE_OCC k_camera_step(BdptGroup G_, int slot, int nres,
                                                                          int shade, LateArgs L, int nlate) {
   const BdptArgs& A = G_.a[blockIdx.y];
   const int b = static_cast<int>(blockIdx.x), nmain = static_cast<int>(gridDim.x) - nlate;
-  if (b < nres) sq_resolve_body(A, slot, b, nres);
-  else if (b >= nmain) late_vertex_body<true>(A, L.l[blockIdx.y], L.n[blockIdx.y], slot, b - nmain, nlate);
-  else if (shade) camera_shade_body(A, slot, b - nres, nmain - nres);
+  if (b < nres) {  // (block-uniform: the resolve reads neither table)
+    sq_resolve_body(A, slot, b, nres);
+    return;
+  }
+  WR_BDPT_TABLES(A)
+  if (b >= nmain) late_vertex_body<true>(A, mats, lights, L.l[blockIdx.y], L.n[blockIdx.y], slot, b - nmain, nlate);
+  else if (shade) camera_shade_body(A, mats, lights, slot, b - nres, nmain - nres);
 }

@@ -20,6 +20,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <cassert>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -599,6 +600,7 @@ struct wr_context {
   size_t api_tmp_n = 0;
   int grid = 2048;
   int cus = 256;
+  int nmats = 0, has_sph = 0;  // entries of ds.mats; the scene has a sphere (BdptArgs)
   float sph_r = 0.f;  // sceneSphere.sceneRadius (scene.cpp:483-487): VCM base radius
   float vcm_cell = 1.f;  // VCM merge-grid cell edge in query half-widths (WR_VCM_CELL); measured 2 -> 1: +4 %
   bool spheres = false;
@@ -748,6 +750,16 @@ int pool_cap(int P, float per, int worst, int floor) {
   return static_cast<int>(std::min<double>(static_cast<double>(worst) * P, std::max<double>(want, floor)));
 }
 
+// BDPT's gen and vertex kernels read the material and light tables from LDS
+// when both fit its caps (wr_bdpt.h, WR_BDPT_TABLES); -DWR_LDS_TABLES=0 builds
+// a library that always reads the global tables (A/B)
+#ifndef WR_LDS_TABLES
+#define WR_LDS_TABLES 1
+#endif
+bool bdpt_lds_tables(int nmats, int nlights) {
+  return WR_LDS_TABLES != 0 && nmats <= kLdsMats && nlights <= kLdsLights;
+}
+
 void layout_bdpt(Arena& a, BdptBuf& B, int P, bool overlapped, bool vcm = false) {
   B.P = P;
   // shadow / aux rays queued by one step, per path: sequential schedule, a
@@ -769,6 +781,12 @@ void layout_bdpt(Arena& a, BdptBuf& B, int P, bool overlapped, bool vcm = false)
   // stored vertices: BDPT's 64-byte BV_* records, VertexCM's 80-byte VS_*
   B.vs = a.take<float>((vcm ? VS_WORDS : BV_WORDS) * sV);
   B.cv = overlapped ? a.take<float>(BV_WORDS * size_t(B.ccap)) : nullptr;
+  // the vertex kernels move these records as 16-byte words, a stored vertex as
+  // one 64-byte line (wr_bdpt.h: BqRec, BvRec)
+  for (const float* r : {B.ls, B.cs, B.vs, B.cv}) {
+    assert(reinterpret_cast<uintptr_t>(r) % 64 == 0);
+    (void)r;
+  }
   B.lvc = vcm ? nullptr : a.take<uint8_t>(sP);
   B.cvc = vcm ? nullptr : a.take<uint8_t>(sP);
   B.vidx = pools ? a.take<int>(size_t(kVMax) * P) : nullptr;
@@ -1839,6 +1857,8 @@ int wr_create(const wr_scene* sc, int device, wr_context** out) {
   d.root_r = v3(s.root_r.x, s.root_r.y, s.root_r.z);
   d.max_stack = std::max(1, s.max_stack);
   c->sph_r = s.sph_r;
+  c->nmats = static_cast<int>(mats.size());
+  c->has_sph = std::any_of(ptype.begin(), ptype.end(), [](int t) { return t != 0; }) ? 1 : 0;
   d.nlights = static_cast<int>(s.lights.size());
   d.lights = dl;
   d.mats = dm;
@@ -2393,6 +2413,8 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
   A0.maxlen = prm->max_path_length > 0 ? prm->max_path_length : 10;
   A0.faithful = prm->faithful;
   A0.overlap = overlap ? 1 : 0;
+  A0.nmats = c->nmats;
+  A0.has_sph = c->has_sph;
   const int maxlen = A0.maxlen;
   const bool count = prm->count_work != 0;
   // One group of pieces on one pipeline, issued step by step: step 0 clears
@@ -2421,6 +2443,12 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
   // bounce b and after them (same stream) resolves the step's shadow / aux
   // rays and shades its camera vertices, which append their extension rays
   // behind the light pass's final count.
+  // the gen and vertex kernels with the material / light tables in LDS, or the
+  // global tables for a scene above the caps (wr_bdpt.h, WR_BDPT_TABLES)
+  const bool gt = !bdpt_lds_tables(c->nmats, c->ds.nlights);
+  const auto k_lgen = gt ? k_light_gen<true> : k_light_gen<false>;
+  const auto k_lshade = gt ? k_light_shade<true> : k_light_shade<false>;
+  const auto k_cstep = gt ? k_camera_step<true> : k_camera_step<false>;
   auto issue_overlap = [&](GroupIssue& G, int step) -> int {
     Pipe& pp = *G.pp;
     const hipStream_t sm = pp.stream;
@@ -2430,7 +2458,7 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     const int g = shade_grid(c, G.nmax);
     if (step == 0) {
       HIPCHK(hipMemsetAsync(pp.sc, 0, gn * sizeof(StepCounters), sm));
-      hipLaunchKernelGGL(k_light_gen, dim3(g, gn), dim3(kShadeBlock), 0, sm, G.GA);
+      hipLaunchKernelGGL(k_lgen, dim3(g, gn), dim3(kShadeBlock), 0, sm, G.GA);
       hipLaunchKernelGGL(k_camera_gen, dim3(g, gn), dim3(kShadeBlock), 0, sm, G.GA);
       tm.mark(WR_K_GEN);
       return WR_OK;
@@ -2451,9 +2479,9 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     trace_launch(c, sm, pp.ctr, tslot(pp, slot), tm, count, ql.Q, ql.max_rays, WR_BDPT_TRACE_MODE, false, nullptr,
                  gn);
     LateArgs L{};
-    if (light) hipLaunchKernelGGL(k_light_shade, dim3(g, gn), dim3(kShadeBlock), 0, sm, G.GA, b, L, 0);
+    if (light) hipLaunchKernelGGL(k_lshade, dim3(g, gn), dim3(kShadeBlock), 0, sm, G.GA, b, L, 0);
     const int nres = shade_grid(c, std::min(G.nmax * (kVMax + 2), pp.bb[0].cap_sq));
-    hipLaunchKernelGGL(k_camera_step, dim3(nres + (more ? g : 0), gn), dim3(kShadeBlock), 0, sm, G.GA, slot, nres,
+    hipLaunchKernelGGL(k_cstep, dim3(nres + (more ? g : 0), gn), dim3(kShadeBlock), 0, sm, G.GA, slot, nres,
                        more ? 1 : 0, L, 0);
     tm.mark(WR_K_SHADE);
     return WR_OK;
@@ -2497,7 +2525,7 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
       if (defer) HIPCHK(hipMemsetAsync(pp.delayed, 0, kGroup * pp.late_paths, sm));
       for (bool& x : G.late) x = false;
       // ---------------- light pass (:67-131)
-      hipLaunchKernelGGL(k_light_gen, dim3(g, gn), dim3(kShadeBlock), 0, sm, G.GA);
+      hipLaunchKernelGGL(k_lgen, dim3(g, gn), dim3(kShadeBlock), 0, sm, G.GA);
       tm.mark(WR_K_GEN);
     } else if (step <= lb_n) {
       const int b = step - 1;
@@ -2510,7 +2538,7 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
       for (int m = 0; m < gn; ++m) ql.add(ext(m, b, bit), A[m].n);
       trace_launch(c, sm, pp.ctr, tslot(pp, b), tm, count, ql.Q, ql.max_rays, WR_BDPT_TRACE_MODE, false,
                    lp ? &L : nullptr, gn);
-      hipLaunchKernelGGL(k_light_shade, dim3(g + (lp ? lg : 0), gn), dim3(kShadeBlock), 0, sm, G.GA, b, L,
+      hipLaunchKernelGGL(k_lshade, dim3(g + (lp ? lg : 0), gn), dim3(kShadeBlock), 0, sm, G.GA, b, L,
                          lp ? lg : 0);
       tm.mark(WR_K_SHADE);
       G.late[b] = bit != 0;
@@ -2536,7 +2564,7 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
       // resolve this step's shadow / aux rays and shade its vertices (and the
       // previous step's deferred ones) in one launch
       const int nres = shade_grid(c, sq_max);
-      hipLaunchKernelGGL(k_camera_step, dim3(nres + (more ? g : 0) + (lp ? lg : 0), gn), dim3(kShadeBlock), 0, sm,
+      hipLaunchKernelGGL(k_cstep, dim3(nres + (more ? g : 0) + (lp ? lg : 0), gn), dim3(kShadeBlock), 0, sm,
                          G.GA, slot, nres, more ? 1 : 0, L, lp ? lg : 0);
       tm.mark(WR_K_SHADE);
       G.late[slot] = bit != 0;

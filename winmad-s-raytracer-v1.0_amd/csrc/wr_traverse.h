@@ -975,6 +975,32 @@ struct Hit {
 };
 // The geometric normal of primitive prim at p (Triangle::hit / Sphere::hit):
 // rebuild_hit's operations, for a stored vertex (wr_bdpt.h stored_bsdf).
+// The forms that take r0 / r1 (the primitive's prim_rec words) and cs (its
+// prim_sph, used only for a sphere) are for a caller that issues those loads
+// with its other loads instead of one behind the other (wr_bdpt.h).
+__device__ __forceinline__ V3 prim_normal(float4 r0, float4 r1, float4 cs, V3 p) {
+  if (__float_as_int(r1.w) != 0) return normalize(p - v3(cs.x, cs.y, cs.z));
+  return normalize(cross(v3(r0.x, r0.y, r0.z), v3(r0.w, r1.x, r1.y)));
+}
+__device__ __forceinline__ Hit rebuild_hit(const DevScene& S, int prim, float t, V3 o, V3 d, float4 r0, float4 r1,
+                                           float4 cs) {
+  Hit h;
+  h.t = t;
+  h.p = o + d * t;
+  h.mat = __float_as_int(r1.z);
+  if (__float_as_int(r1.w) != 0) {
+    h.n = normalize(h.p - v3(cs.x, cs.y, cs.z));
+    float tt;
+    int in = 0;
+    sph_hit(S, prim, o, d, 0.f, WR_INF, tt, &in);
+    h.inside = in;
+  } else {
+    // (p1 - p0) x (p2 - p0) == (p0 - p1) x (p0 - p2) exactly
+    h.n = normalize(cross(v3(r0.x, r0.y, r0.z), v3(r0.w, r1.x, r1.y)));
+    h.inside = (dot(d, h.n) < WR_EPS) ? 0 : 1;
+  }
+  return h;
+}
 __device__ __forceinline__ V3 prim_normal(const DevScene& S, int prim, V3 p) {
   const float4 r0 = S.prim_rec[2 * static_cast<size_t>(prim)], r1 = S.prim_rec[2 * static_cast<size_t>(prim) + 1];
   if (__float_as_int(r1.w) != 0) {
