@@ -312,6 +312,56 @@ int wr_path_radiance(wr_context* ctx, const wr_ray* rays, int64_t n, int32_t max
  * film as wr_render_bdpt (pre-transpose, accumulated, not scaled). */
 int wr_render_vcm(wr_context* ctx, const wr_vcm_params* p, float* film, int film_on_device, wr_stats* stats);
 
+/* ---- second-moment films and the error estimate (no reference
+ * counterpart: the reference keeps only the sum).  A *pass* is the unit whose
+ * films are independent estimates of the image:
+ *   BDPT / VCM: one iteration (global index iter_begin + i), whole frame, with
+ *     the light-tracing splats it lands on other pixels;
+ *   PT: one sample index k of the spp grid, whole frame, unscaled.
+ * With F_i the film of pass i alone, a moments render accumulates
+ *   film    += sum_i F_i          (exactly what the plain render adds)
+ *   film_sq += sum_i F_i o F_i    (per value, of the complete pass film)
+ * into two caller films of height*width*3 floats, same layout, both host or
+ * both device (films_on_device).  Both accumulate, so calls over disjoint pass
+ * ranges add up: resume, sharding over ranks, wr_film_reduce of film_sq.
+ * Otherwise as the plain calls (ordering, stats, the BDPT redo, which puts both
+ * films back).  A moments render keeps every piece of an iteration on one
+ * pipeline, which holds 2 pass films of the frame's size (allocated by the
+ * first moments render, kept on the context); a plain render allocates none.
+ * On a wr_create_multi context: WR_E_ARG (it shares one iteration out over
+ * its devices).
+ * PT: the samples of a pixel are strata of one grid (sampler.cpp:28-42), not
+ * i.i.d. passes: film_sq / wr_film_error then give a conservative estimate
+ * (stratification only lowers the variance of the mean), and a PT render
+ * cannot stop early without leaving part of each pixel unsampled.
+ * Callers detect these entry points by their symbols (WR_API_VERSION stays 8). */
+int wr_render_bdpt_moments(wr_context* ctx, const wr_bdpt_params* p, float* film, float* film_sq,
+                           int films_on_device, wr_stats* stats);
+int wr_render_vcm_moments(wr_context* ctx, const wr_vcm_params* p, float* film, float* film_sq,
+                          int films_on_device, wr_stats* stats);
+int wr_render_path_moments(wr_context* ctx, const wr_path_params* p, float* film, float* film_sq,
+                           int films_on_device, wr_stats* stats);
+
+/* Standard error of the mean image from the two films of n_passes passes.  Per
+ * value, in double from the float inputs (in float, Q - S^2/n of a value that
+ * barely varies cancels to noise):
+ *   mu = S / n,  var_of_mean = max(0, (Q - S^2 / n) / (n - 1)) / n,
+ *   se = sqrt(var_of_mean)                      (S = film, Q = film_sq). */
+typedef struct {
+  double sum_stderr;      /* sum of se over all values                            */
+  double sum_mean;        /* sum of mu over all values                            */
+  double rel_stderr;      /* sum_stderr / sum_mean, 0 if the film is black        */
+  double max_rel_stderr;  /* largest se / mu over the values with mu > 0          */
+  int64_t values;         /* number of values with mu > 0                         */
+} wr_error_info;
+/* Host films (films_on_device == 0): a plain loop on the CPU; ctx may be NULL
+ * and no device is needed.  Device films: a kernel on the context's device,
+ * ordered like a render.  stderr_map (or NULL): height*width*3 floats in the
+ * films' memory space, overwritten with se.  WR_E_ARG: n_passes < 2, a null
+ * film or `out`, device films without a context. */
+int wr_film_error(wr_context* ctx, const float* film, const float* film_sq, int width, int height, int n_passes,
+                  int films_on_device, float* stderr_map, wr_error_info* out);
+
 /* ---- output (ImageFilm::outputImage, scene/film.cpp:39-64; BDPT transpose
  * bidirPathTracing.cpp:29-46) ---- scale -> clamp [0,1] -> pow(1/gamma) ->
  * (uchar)(x*255.0); binary PPM (RGB).  transpose != 0 swaps [i][j] <-> [j][i]

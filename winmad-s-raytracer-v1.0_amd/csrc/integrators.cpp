@@ -71,7 +71,8 @@ uint64_t SurfaceIntegrator::settingsHash(const std::vector<double>& settings) co
 }
 
 template <class Batch>
-void SurfaceIntegrator::batched(int kind, int total, uint32_t seed, const std::vector<double>& settings, Batch batch) {
+void SurfaceIntegrator::batched(int kind, int total, uint32_t seed, const std::vector<double>& settings, Batch batch,
+                                int every) {
   int done = 0;
   stopped = false;
   const uint64_t fp = settingsHash(settings);
@@ -100,19 +101,59 @@ void SurfaceIntegrator::batched(int kind, int total, uint32_t seed, const std::v
   while (done < total) {
     int n = total - done;
     if (checkpointEvery > 0) n = std::min(n, checkpointEvery);
+    if (every > 0) n = std::min(n, every);
     if (stopAfter >= 0) n = std::min(n, stopAfter - done);
     if (n <= 0) {
       stopped = true;
       return;
     }
-    batch(done, n);
+    const bool enough = batch(done, n);
     done += n;
     if (!checkpointPath.empty()) {
       want.done = done;
       ok(wr_checkpoint_save(checkpointPath.c_str(), &want, film.data()));
     }
+    if (enough) return;
   }
 }
+
+namespace {
+// the part of render() the two iteration-based integrators share: a batch is
+// rendered by plain(begin, count) or moments(begin, count), then the stop rule
+template <class Plain, class Moments>
+bool error_batch(SurfaceIntegrator& si, ErrorTarget& et, wr_context* ctx, int begin, int count, Plain plain,
+                 Moments moments) {
+  if (!(et.errorTarget > 0.0)) {
+    plain(begin, count);
+    et.iterationsDone = begin + count;
+    return false;
+  }
+  moments(begin, count);
+  et.iterationsDone = begin + count;
+  if (et.iterationsDone < 2) return false;
+  ok(wr_film_error(ctx, si.film.data(), et.filmSq.data(), si.width, si.height, et.iterationsDone, 0, nullptr,
+                   &et.errorInfo));
+  return et.errorInfo.rel_stderr <= et.errorTarget;
+}
+void error_begin(SurfaceIntegrator& si, ErrorTarget& et) {
+  et.iterationsDone = 0;
+  et.errorInfo = wr_error_info{};
+  if (!(et.errorTarget > 0.0)) return;
+  if (!si.checkpointPath.empty())
+    throw std::runtime_error("errorTarget cannot be combined with a checkpoint: the file does not carry filmSq");
+  if (et.errorCheckEvery < 1) throw std::runtime_error("errorCheckEvery must be at least 1");
+  et.filmSq.assign(si.film.size(), 0.f);
+}
+void error_map(SurfaceIntegrator& si, ErrorTarget& et, const char* filename) {
+  if (et.filmSq.size() != si.film.size() || et.iterationsDone < 2)
+    throw std::runtime_error("no error map: render with errorTarget > 0 and at least 2 iterations first");
+  std::vector<float> map(si.film.size());
+  wr_error_info info{};
+  ok(wr_film_error(nullptr, si.film.data(), et.filmSq.data(), si.width, si.height, et.iterationsDone, 0, map.data(),
+                   &info));
+  ok(wr_film_write_image(map.data(), si.height, si.width, 1.f, 2.2f, si.height == si.width, filename));
+}
+}  // namespace
 
 void BidirPathTracing::init(const char* filename, Parameters& para) {
   samplesPerPixel = para.SAMPLES_PER_PIXEL;  // stored, unused by BDPT (:11)
@@ -123,6 +164,7 @@ void BidirPathTracing::init(const char* filename, Parameters& para) {
 }
 
 void BidirPathTracing::render() {
+  error_begin(*this, *this);
   batched(WR_CKPT_BDPT, iterations, seed, {double(maxPathLength), double(controlLength)}, [&](int begin, int count) {  // :25-26
     wr_bdpt_params p{};
     p.width = width;
@@ -133,15 +175,20 @@ void BidirPathTracing::render() {
     p.max_path_length = maxPathLength;
     p.seed = seed;
     p.faithful = 1;
-    ok(wr_render_bdpt(ctx_, &p, film.data(), 0, &stats));
-  });
+    return error_batch(*this, *this, ctx_, begin, count,
+                       [&](int, int) { ok(wr_render_bdpt(ctx_, &p, film.data(), 0, &stats)); },
+                       [&](int, int) { ok(wr_render_bdpt_moments(ctx_, &p, film.data(), filmSq.data(), 0, &stats)); });
+  }, errorTarget > 0.0 ? errorCheckEvery : 0);
 }
 
 void BidirPathTracing::outputImage(const char* filename) {
   // The reference transposes in place assuming height == width (:31-44);
   // only square films are transposed here (non-square reference output is corrupt).
-  ok(wr_film_write_image(film.data(), height, width, 1.f / iterations, 2.2f, height == width, filename));
+  const int n = iterationsDone > 0 ? iterationsDone : iterations;
+  ok(wr_film_write_image(film.data(), height, width, 1.f / n, 2.2f, height == width, filename));
 }
+
+void BidirPathTracing::outputErrorMap(const char* filename) { error_map(*this, *this, filename); }
 
 void VertexCM::init(const char* filename, Parameters& para) {
   samplesPerPixel = para.SAMPLES_PER_PIXEL;  // stored, unused (:9)
@@ -152,6 +199,7 @@ void VertexCM::init(const char* filename, Parameters& para) {
 }
 
 void VertexCM::render() {
+  error_begin(*this, *this);
   batched(WR_CKPT_VCM, iterations, seed, {double(minPathLength), double(maxPathLength), double(baseRadiusFactor), double(radiusAlpha)}, [&](int begin, int count) {
     wr_vcm_params p{};
     p.width = width;
@@ -163,14 +211,19 @@ void VertexCM::render() {
     p.radius_factor = baseRadiusFactor;
     p.radius_alpha = radiusAlpha;
     p.seed = seed;
-    ok(wr_render_vcm(ctx_, &p, film.data(), 0, &stats));
-  });
+    return error_batch(*this, *this, ctx_, begin, count,
+                       [&](int, int) { ok(wr_render_vcm(ctx_, &p, film.data(), 0, &stats)); },
+                       [&](int, int) { ok(wr_render_vcm_moments(ctx_, &p, film.data(), filmSq.data(), 0, &stats)); });
+  }, errorTarget > 0.0 ? errorCheckEvery : 0);
 }
 
 void VertexCM::outputImage(const char* filename) {
   // transpose (square films only, :31-42), scale 1/iterations, gamma 2.2 (:44)
-  ok(wr_film_write_image(film.data(), height, width, 1.f / iterations, 2.2f, height == width, filename));
+  const int n = iterationsDone > 0 ? iterationsDone : iterations;
+  ok(wr_film_write_image(film.data(), height, width, 1.f / n, 2.2f, height == width, filename));
 }
+
+void VertexCM::outputErrorMap(const char* filename) { error_map(*this, *this, filename); }
 
 void PathIntegrator::init(const char* filename, Parameters& para) {
   maxTracingDepth = para.MAX_TRACING_DEPTH;
@@ -194,6 +247,7 @@ void PathIntegrator::render() {
     p.sample_count = count;
     p.seed = seed;
     ok(wr_render_path(ctx_, &p, film.data(), 0, &stats));
+    return false;
   });
   if (stopped) return;
   const float inv = 1.f / samplesPerPixel;  // film->scale(1.f / samplesPerPixel) (:45)

@@ -60,16 +60,36 @@ class SurfaceIntegrator {
   void load(const char* filename);
   // the render loop in batches: renders [done, total) through batch(begin, count),
   // resuming from / saving checkpoints of `kind`
+  // (every > 0: batches of at most `every`; a batch that returns true ends the render)
   template <class Batch>
-  void batched(int kind, int total, uint32_t seed, const std::vector<double>& settings, Batch batch);
+  void batched(int kind, int total, uint32_t seed, const std::vector<double>& settings, Batch batch, int every = 0);
   // hash of the scene (wr_scene_fingerprint) and `settings`: stored in the
   // checkpoint, a resume with another scene or settings is refused
   uint64_t settingsHash(const std::vector<double>& settings) const;
 };
 
-// src/surfaceIntegrator/bidirPathTracing.{h,cpp}
-class BidirPathTracing : public SurfaceIntegrator {
+// Noise-target stopping of the iteration-based integrators (no reference
+// counterpart; winmad_rt.h, second-moment films).  With errorTarget > 0,
+// render() runs wr_render_*_moments in batches of errorCheckEvery iterations,
+// asks wr_film_error after each and stops at the first batch boundary where
+// rel_stderr <= errorTarget, or at `iterations`.  iterationsDone is what the
+// film holds; outputImage scales by 1 / iterationsDone.  Not combined with a
+// checkpoint (the file does not carry filmSq): render() throws.
+class ErrorTarget {
  public:
+  double errorTarget = 0.0;  // 0 = off: render() is the plain render
+  int errorCheckEvery = 4;   // iterations per batch
+  int iterationsDone = 0;
+  wr_error_info errorInfo{};  // of the last check (zero before the second iteration)
+  std::vector<float> filmSq;  // sum of the squared iteration films (errorTarget > 0)
+};
+
+// src/surfaceIntegrator/bidirPathTracing.{h,cpp}
+class BidirPathTracing : public SurfaceIntegrator, public ErrorTarget {
+ public:
+  // the standard-error map of the film (errorTarget > 0, >= 2 iterations), as
+  // outputImage writes the film: transposed when square; .pfm keeps the floats
+  void outputErrorMap(const char* filename);
   int minPathLength = 0, maxPathLength = 10, controlLength = 3;
   int iterations = 1;  // bidirPathTracing.cpp:9
   uint32_t seed = 5489;
@@ -79,8 +99,9 @@ class BidirPathTracing : public SurfaceIntegrator {
 };
 
 // src/surfaceIntegrator/vertexcm.{h,cpp}
-class VertexCM : public SurfaceIntegrator {
+class VertexCM : public SurfaceIntegrator, public ErrorTarget {
  public:
+  void outputErrorMap(const char* filename);
   int minPathLength = 0, maxPathLength = 10;
   int iterations = 1;            // vertexcm.cpp:7
   float baseRadiusFactor = 0.003f;  // baseRadius = 0.003 * sceneRadius (:13)

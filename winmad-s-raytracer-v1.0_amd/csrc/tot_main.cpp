@@ -3,6 +3,13 @@
 //     wr_tot <scene> <out.ppm> -bpt|-vcm|-p [--params FILE] [--iterations N] [--seed S]
 //            [--device D | --gpus N | --devices D0,D1,...] [--trace bvh|reference]
 //            [--checkpoint FILE [--checkpoint-every N] [--stop-after N]] [--hw-queues N]
+//            [--target-error X [--error-every N] [--error-out map.pfm]]
+// --target-error X (-bpt / -vcm): render in batches of N iterations (default 4)
+// and stop at the first batch boundary where the film's relative standard error
+// (wr_film_error's rel_stderr) is at most X, or at --iterations; 0 = off.
+// Prints `error <rel_stderr> after <n> iterations`; --error-out writes the
+// standard-error map.  Not for -p (its samples are strata of one grid, not
+// independent passes) and not together with --checkpoint.
 // Parameters come from src/parameters.para relative to the CWD, as in the
 // reference (main.cpp:32), unless --params is given.  Writes time.txt like
 // main.cpp:93-95 (seconds instead of clock ticks).
@@ -42,12 +49,17 @@ int main(int argc, char** argv) {
     std::fprintf(stderr,
                  "usage: %s <scene> <out.ppm> -bpt|-vcm|-p [--params F] [--iterations N] [--seed S] "
                  "[--device D | --gpus N | --devices D0,D1,..] [--trace bvh|reference] "
-                 "[--checkpoint F [--checkpoint-every N] [--stop-after N]] [--hw-queues N]\n",
+                 "[--checkpoint F [--checkpoint-every N] [--stop-after N]] [--hw-queues N] "
+                 "[--target-error X [--error-every N] [--error-out map.pfm]]\n",
                  argv[0]);
     return 2;
   }
   const char* params = "src/parameters.para";
   const char* checkpoint = nullptr;
+  const char* error_out = nullptr;
+  double target_error = 0.0;
+  bool have_target = false;
+  int error_every = 4;
   int iterations = 1, device = 0, gpus = 0, every = 0, stop_after = -1, hw_queues = 16;
   std::vector<int> devices;
   unsigned seed = 5489;
@@ -67,8 +79,26 @@ int main(int argc, char** argv) {
       else if (!std::strcmp(a, "--checkpoint-every")) every = std::atoi(v);
       else if (!std::strcmp(a, "--stop-after")) stop_after = std::atoi(v);
       else if (!std::strcmp(a, "--hw-queues")) hw_queues = std::atoi(v);
+      else if (!std::strcmp(a, "--target-error")) {
+        char* end = nullptr;
+        target_error = std::strtod(v, &end);
+        have_target = true;
+        if (end == v || *end || !(target_error >= 0.0))
+          throw std::runtime_error(std::string("usage: --target-error takes a number >= 0 (0 = off), not ") + v);
+      } else if (!std::strcmp(a, "--error-every")) {
+        error_every = std::atoi(v);
+        if (error_every < 1) throw std::runtime_error("usage: --error-every takes a number of iterations >= 1");
+      } else if (!std::strcmp(a, "--error-out")) error_out = v;
       else throw std::runtime_error(std::string("unknown option ") + a);
     }
+    if (have_target && !std::strcmp(argv[3], "-p"))
+      throw std::runtime_error("usage: --target-error is for -bpt and -vcm: the samples of -p are strata of one "
+                               "grid, stopping early would leave part of each pixel unsampled");
+    if (target_error > 0.0 && checkpoint)
+      throw std::runtime_error("usage: --target-error cannot be combined with --checkpoint "
+                               "(the checkpoint file does not carry the squared film)");
+    if (error_out && !(target_error > 0.0))
+      throw std::runtime_error("usage: --error-out needs --target-error X with X > 0");
   } catch (const std::exception& e) {
     std::fprintf(stderr, "%s\n", e.what());
     return 2;
@@ -85,15 +115,18 @@ int main(int argc, char** argv) {
     para.load_parameters(params);
     auto t0 = std::chrono::steady_clock::now();
     std::unique_ptr<winmad::SurfaceIntegrator> integ;
+    winmad::ErrorTarget* et = nullptr;
     if (!std::strcmp(argv[3], "-bpt")) {
       auto* b = new winmad::BidirPathTracing();
       b->iterations = iterations;
       b->seed = seed;
+      et = b;
       integ.reset(b);
     } else if (!std::strcmp(argv[3], "-vcm")) {  // main.cpp:53-58
       auto* v = new winmad::VertexCM();
       v->iterations = iterations;
       v->seed = seed;
+      et = v;
       integ.reset(v);
     } else if (!std::strcmp(argv[3], "-p")) {
       auto* p = new winmad::PathIntegrator();
@@ -102,6 +135,10 @@ int main(int argc, char** argv) {
     } else {
       std::printf("error!\n");  // main.cpp:88-91
       return 1;
+    }
+    if (et) {
+      et->errorTarget = target_error;
+      et->errorCheckEvery = error_every;
     }
     integ->device = device;
     integ->devices = devices;
@@ -126,6 +163,13 @@ int main(int argc, char** argv) {
       return 0;
     }
     integ->outputImage(argv[2]);
+    if (et && target_error > 0.0) {
+      std::printf("error %.6g after %d iterations\n", et->errorInfo.rel_stderr, et->iterationsDone);
+      if (error_out) {
+        if (auto* b = dynamic_cast<winmad::BidirPathTracing*>(integ.get())) b->outputErrorMap(error_out);
+        else if (auto* v = dynamic_cast<winmad::VertexCM*>(integ.get())) v->outputErrorMap(error_out);
+      }
+    }
     double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (FILE* f = std::fopen("time.txt", "w")) {
       std::fprintf(f, "time = %.6f s\n", sec);

@@ -576,6 +576,10 @@ struct Pipe {
   LateList late_h[kGroup][2]{};          // host copies: [member][step parity]
   LateList* late_d = nullptr;            // device copies, same order
   uint8_t* delayed = nullptr;            // [kGroup][late_paths]
+  // moments renders only (wr_render_*_moments): the films of the passes this
+  // pipeline has open, zero between passes (k_film_fold clears what it folds)
+  float* mom[kGroup]{};
+  size_t mom_n = 0;  // floats each
 };
 
 struct wr_context {
@@ -595,6 +599,8 @@ struct wr_context {
   size_t film_tmp_n = 0;
   float* film_bak = nullptr;  // a device film as it was before a BDPT render (redone on pool overflow)
   size_t film_bak_n = 0;
+  bool mom_dirty = false;  // a moments render failed under way: its pass films are cleared before the next
+  double* err_acc = nullptr;  // wr_film_error on device films: sum se, sum mu, max se / mu (bits), values
   DevCounters* host_ctr = nullptr;  // pinned: the pipelines' counters after a render (finish_render)
   char* api_tmp = nullptr;  // wr_trace_closest / wr_occluded / wr_path_radiance scratch, grown on demand
   size_t api_tmp_n = 0;
@@ -724,6 +730,113 @@ const RcclApi& rccl() {
 // films of a multi-device render, summed on devices[0] (peer-copy path)
 __global__ void __launch_bounds__(256) k_film_accumulate(float* dst, const float* src, size_t n) {
   for (size_t i = blockIdx.x * size_t(256) + threadIdx.x; i < n; i += size_t(gridDim.x) * 256) dst[i] += src[i];
+}
+
+// ---- moments renders (wr_render_*_moments).  A pass (one BDPT /
+// VCM iteration, one PT sample index, whole frame) renders into a film of its
+// own on its pipeline; when its last piece has run, k_film_fold adds the pass
+// film into the caller's `film` and its square, per value, into `film_sq`, and
+// clears it for the pipeline's next pass.  Several pipelines fold into the same
+// two films at once, hence the float atomics of the splat kernels (film_add).
+// A block moves 1024 floats per round: 16-byte loads, turned through LDS so
+// that a wave's atomics cover 256 contiguous bytes (the shape global float
+// atomics run fastest in); zeros (84 % of a torus film) take no atomic.
+constexpr int kFoldBlock = 256;
+__global__ void __launch_bounds__(kFoldBlock) k_film_fold(float* __restrict__ film, float* __restrict__ film_sq,
+                                                          float* __restrict__ pass, size_t n) {
+  __shared__ float tile[4 * kFoldBlock];
+  const size_t rounds = n / (4 * kFoldBlock);
+  const int t = threadIdx.x;
+  for (size_t r = blockIdx.x; r < rounds; r += gridDim.x) {
+    const size_t base = r * (4 * kFoldBlock);
+    float4* src = reinterpret_cast<float4*>(pass + base) + t;
+    const float4 v = *src;
+    reinterpret_cast<float4*>(tile)[t] = v;
+    if (v.x != 0.f || v.y != 0.f || v.z != 0.f || v.w != 0.f) *src = make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float x = tile[k * kFoldBlock + t];
+      if (x != 0.f) {
+        atomicAdd(film + base + k * kFoldBlock + t, x);
+        atomicAdd(film_sq + base + k * kFoldBlock + t, x * x);
+      }
+    }
+    __syncthreads();
+  }
+  // the tail: 3 P floats need not be a multiple of the round
+  for (size_t i = rounds * (4 * kFoldBlock) + blockIdx.x * size_t(kFoldBlock) + t; i < n;
+       i += size_t(gridDim.x) * kFoldBlock) {
+    const float x = pass[i];
+    if (x != 0.f) {
+      atomicAdd(film + i, x);
+      atomicAdd(film_sq + i, x * x);
+      pass[i] = 0.f;
+    }
+  }
+}
+
+// Standard error of the mean of n passes, per value, from the sum S and the
+// sum of squares Q (wr_film_error): mu = S / n, var(mean) = max(0, (Q - S^2 / n)
+// / (n - 1)) / n, se = sqrt(var).  In double: in float Q - S^2 / n of a value
+// that barely varies cancels to rounding noise of order 1e-7 Q.  acc: sum se,
+// sum mu, max se / mu over the values with mu > 0 (as the bits of a
+// non-negative double, which order like the doubles), their number.
+__host__ __device__ inline void film_error_value(float S, float Q, double n, double* mu, double* se) {
+  const double s = static_cast<double>(S), q = static_cast<double>(Q);
+  double var = (q - s * s / n) / (n - 1.0);
+  var = (var > 0.0 ? var : 0.0) / n;  // (a NaN input gives 0, not NaN)
+  *mu = s / n;
+  *se = sqrt(var);
+}
+constexpr int kErrBlock = 256;
+__global__ void __launch_bounds__(kErrBlock) k_film_error(const float* __restrict__ film,
+                                                         const float* __restrict__ film_sq, size_t n, int passes,
+                                                         float* __restrict__ se_map, double* __restrict__ acc) {
+  double sum_se = 0.0, sum_mu = 0.0, max_rel = 0.0;
+  unsigned long long cnt = 0;
+  const double np = static_cast<double>(passes);
+  for (size_t i = blockIdx.x * size_t(kErrBlock) + threadIdx.x; i < n; i += size_t(gridDim.x) * kErrBlock) {
+    double mu, se;
+    film_error_value(film[i], film_sq[i], np, &mu, &se);
+    if (se_map) se_map[i] = static_cast<float>(se);
+    sum_se += se;
+    sum_mu += mu;
+    if (mu > 0.0) {
+      const double rel = se / mu;
+      max_rel = rel > max_rel ? rel : max_rel;
+      ++cnt;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    sum_se += __shfl_xor(sum_se, o);
+    sum_mu += __shfl_xor(sum_mu, o);
+    const double m = __shfl_xor(max_rel, o);
+    max_rel = m > max_rel ? m : max_rel;
+    cnt += __shfl_xor(cnt, o);
+  }
+  __shared__ double red[kErrBlock / 64][4];
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[w][0] = sum_se;
+    red[w][1] = sum_mu;
+    red[w][2] = max_rel;
+    red[w][3] = static_cast<double>(cnt);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0, b = 0.0, m = 0.0, k = 0.0;
+    for (int j = 0; j < kErrBlock / 64; ++j) {
+      a += red[j][0];
+      b += red[j][1];
+      m = red[j][2] > m ? red[j][2] : m;
+      k += red[j][3];
+    }
+    atomicAdd(acc + 0, a);
+    atomicAdd(acc + 1, b);
+    atomicMax(reinterpret_cast<unsigned long long*>(acc + 2), static_cast<unsigned long long>(__double_as_longlong(m)));
+    atomicAdd(acc + 3, k);
+  }
 }
 
 // overlapped: the BDPT render's own layout (the camera pass's extension queues
@@ -1317,15 +1430,23 @@ void cut_pieces(int64_t a, int64_t b, int P, int unit, int cap, std::vector<Piec
 // unevenly into two groups per pipeline, so that the pipelines' late bounces
 // fall at different times, measured worse: C2 at 20 iterations 2,292 ->
 // 1,850 Mrays/s -- each extra group pays the bounce tails again.)
-PiecePlan plan_pieces(int64_t lo, int64_t hi, int P, int unit, int cap, int np, int min_piece) {
+// whole_iters (moments renders; lo, hi at iteration ends): shares are cut at
+// iteration ends only, so every piece of an iteration runs on one pipeline, in
+// order, and the iteration's film is complete there when its last piece has run.
+PiecePlan plan_pieces(int64_t lo, int64_t hi, int P, int unit, int cap, int np, int min_piece,
+                      bool whole_iters = false) {
   PiecePlan plan;
   const int64_t T = hi - lo;
   if (T <= 0) {
     plan.per_pipe.resize(1);
     return plan;
   }
-  const int64_t shares = std::max<int64_t>(1, std::min<int64_t>(np, T / std::max(1, min_piece)));
-  auto bound = [&](int64_t k) { return k == shares ? hi : flat_round(lo + k * T / shares, P, unit); };
+  int64_t shares = std::max<int64_t>(1, std::min<int64_t>(np, T / std::max(1, min_piece)));
+  if (whole_iters) shares = std::min<int64_t>(shares, T / P);
+  auto bound = [&](int64_t k) {
+    if (whole_iters) return lo + (k * (T / P) / shares) * P;
+    return k == shares ? hi : flat_round(lo + k * T / shares, P, unit);
+  };
   auto groups_of = [&](const std::vector<Piece>& pcs, std::vector<std::vector<Piece>>& gs) {
     for (size_t i = 0; i < pcs.size(); i += kGroup)
       gs.emplace_back(pcs.begin() + i, pcs.begin() + std::min(pcs.size(), i + kGroup));
@@ -2084,12 +2205,15 @@ void wr_destroy(wr_context* c) {
     if (p.ctr) (void)hipFree(p.ctr);
     if (p.sc) (void)hipFree(p.sc);
     p.work.release();
+    for (float* f : p.mom)
+      if (f) (void)hipFree(f);
     if (p.stream && p.stream != c->stream) (void)hipStreamDestroy(p.stream);
   }
   if (c->t_ref) (void)hipEventDestroy(c->t_ref);
   if (c->t_null) (void)hipEventDestroy(c->t_null);
   if (c->film_tmp) (void)hipFree(c->film_tmp);
   if (c->film_bak) (void)hipFree(c->film_bak);
+  if (c->err_acc) (void)hipFree(c->err_acc);
   if (c->host_ctr) (void)hipHostFree(c->host_ctr);
   if (c->api_tmp) (void)hipFree(c->api_tmp);
   if (c->api_t2) (void)hipFree(c->api_t2);
@@ -2252,6 +2376,63 @@ static int film_return(wr_context* c, float* film, int film_on_device, size_t nf
   return WR_OK;
 }
 
+// ---- moments renders: the caller's two films and the pipelines' pass films.
+// Host films share one device block of 2 nf floats (film, then film_sq).
+struct MomentFilms {
+  float* sq = nullptr;   // the caller's film_sq (nullptr: a plain render)
+  float* dsq = nullptr;  // its device film
+  bool on() const { return sq != nullptr; }
+};
+static int moments_target(wr_context* c, float* film, MomentFilms& M, int films_on_device, size_t nf, float** dev) {
+  if (!M.on()) return film_target(c, film, films_on_device, nf, dev);
+  if (int rc = film_target(c, film, films_on_device, 2 * nf, dev)) return rc;
+  M.dsq = films_on_device ? M.sq : *dev + nf;
+  return WR_OK;
+}
+static int moments_return(wr_context* c, float* film, const MomentFilms& M, int films_on_device, size_t nf) {
+  if (!M.on()) return film_return(c, film, films_on_device, nf);
+  if (films_on_device) return WR_OK;
+  std::vector<float> tmp(2 * nf);
+  HIPCHK(hipMemcpyAsync(tmp.data(), c->film_tmp, 2 * nf * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < nf; ++i) film[i] = film[i] + tmp[i];
+  for (size_t i = 0; i < nf; ++i) M.sq[i] = M.sq[i] + tmp[nf + i];
+  return WR_OK;
+}
+// kGroup pass films of nf floats on each of the pipelines [0, np), zero.  On the
+// context stream, which every pipeline waits for at begin_render.  Only moments
+// renders come here: a plain render allocates none of this.
+static int ensure_moments(wr_context* c, int np, size_t nf) {
+  const bool dirty = c->mom_dirty;  // a moments render failed under way: its launches may still run
+  if (dirty) HIPCHK(hipDeviceSynchronize());
+  for (int i = 0; i < kMaxPipes; ++i) {
+    Pipe& p = c->pipes[i];
+    const bool grow = i < np && p.mom_n < nf;
+    if (!grow && !(dirty && p.mom_n)) continue;
+    const size_t had = p.mom_n;
+    if (grow) p.mom_n = 0;
+    for (int m = 0; m < kGroup; ++m) {
+      if (grow) {
+        if (p.mom[m]) (void)hipFree(p.mom[m]);
+        p.mom[m] = nullptr;
+        HIPCHK(hipMalloc(&p.mom[m], nf * sizeof(float)));
+      }
+      HIPCHK(hipMemsetAsync(p.mom[m], 0, (grow ? nf : had) * sizeof(float), c->stream));
+    }
+    if (grow) p.mom_n = nf;
+  }
+  c->mom_dirty = false;
+  return WR_OK;
+}
+// fold pass film m of the pipeline into the caller's films, behind the pass's
+// last launch on the pipeline's stream
+static void fold_launch(wr_context* c, Pipe& pp, int m, float* dfilm, float* dsq, size_t nf) {
+  const size_t rounds = (nf + 4 * kFoldBlock - 1) / (4 * kFoldBlock);
+  const int g = static_cast<int>(std::max<size_t>(1, std::min<size_t>(rounds, size_t(c->cus) * 8)));
+  hipLaunchKernelGGL(k_film_fold, dim3(g), dim3(kFoldBlock), 0, pp.stream, dfilm, dsq, pp.mom[m], nf);
+  Timer(c, &pp).mark(WR_K_OTHER);
+}
+
 // Issues one round of launches: step by step across the pipelines [0, np),
 // on c->issue_threads host threads (pipeline i on thread i % T, each thread
 // stepping through its own pipelines; their streams are independent).
@@ -2319,8 +2500,10 @@ static int bdpt_unit(const wr_bdpt_params* prm) {
 }
 // One device: the flattened path-iterations [f_lo, f_hi) of the render
 // (iteration iter_begin + f / P, path f % P; whole units).
+// film_sq != nullptr: a moments render (whole iterations per pipeline, each into
+// a pass film that is folded into film / film_sq when the iteration is done).
 static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_lo, int64_t f_hi, float* film,
-                           int film_on_device, wr_stats* st) {
+                           int film_on_device, wr_stats* st, float* film_sq = nullptr) {
   HIPCHK(hipSetDevice(c->device));
   const double t0 = host_now();
   const int P = prm->width * prm->height;
@@ -2329,7 +2512,9 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
   const int cap = piece_capacity(c, P, unit);
   const int fit = pipelines_that_fit(c, 1, cap, kGroup, c->npipes);
   if (fit < 1) return WR_E_HIP;  // message set by the allocation
-  const PiecePlan plan = plan_pieces(f_lo, f_hi, P, unit, cap, fit, c->piece_min);
+  MomentFilms M;
+  M.sq = film_sq;
+  const PiecePlan plan = plan_pieces(f_lo, f_hi, P, unit, cap, fit, c->piece_min, M.on());
   const int np = plan.pipes();
   // a render too short to fill the pipelines that fit, each holding one
   // group, is latency-bound: its searches take the 4-wide tree when the scene
@@ -2382,7 +2567,10 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
       if (int rc = ensure_late(c->pipes[i], cap, late_records(cap))) return rc;
   float* dfilm = nullptr;
   const size_t nf = size_t(P) * 3;
-  if (int rc = film_target(c, film, film_on_device, nf, &dfilm)) return rc;
+  if (int rc = moments_target(c, film, M, film_on_device, nf, &dfilm)) return rc;
+  if (M.on())
+    if (int rc = ensure_moments(c, fit, nf)) return rc;
+  const size_t nbak = M.on() ? 2 * nf : nf;  // film_bak: film, then film_sq
   // vertex pools and shadow queues sized by use (BdptBuf): a render that fills
   // one is redone from the film as it was before it.  A caller's device film is
   // copied first (after the caller's work on the null stream, before any
@@ -2390,16 +2578,18 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
   // host film's device copy starts at zero
   const bool pooled = c->pipes[0].bb[0].vidx != nullptr;
   if (pooled && film_on_device) {
-    if (c->film_bak_n < nf) {
+    if (c->film_bak_n < nbak) {
       if (c->film_bak) (void)hipFree(c->film_bak);
       c->film_bak = nullptr;
       c->film_bak_n = 0;
-      HIPCHK(hipMalloc(&c->film_bak, nf * sizeof(float)));
-      c->film_bak_n = nf;
+      HIPCHK(hipMalloc(&c->film_bak, nbak * sizeof(float)));
+      c->film_bak_n = nbak;
     }
     (void)hipEventRecord(c->t_null, nullptr);
     (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
     HIPCHK(hipMemcpyAsync(c->film_bak, dfilm, nf * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if (M.on())
+      HIPCHK(hipMemcpyAsync(c->film_bak + nf, M.dsq, nf * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   }
   const wr_stats st0 = st ? *st : wr_stats{};
   BdptArgs A0;
@@ -2426,6 +2616,7 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     BdptGroup GA;
     int gn = 0, nmax = 0;
     bool late[kSlots] = {};  // late work issued at step slot
+    int fold[kGroup] = {}, nfold = 0;  // moments: the pass films complete after this group
   };
   // steps: light gen, light bounces b = 0 .. lb_n - 1, camera gen, camera bounces b = 0 .. maxlen;
   // overlapped: both gens, then bounces b = 0 .. maxlen of both passes together
@@ -2487,6 +2678,10 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     return WR_OK;
   };
   auto issue = [&](GroupIssue& G, int step) -> int {
+    if (step == nsteps) {  // moments renders: one step more
+      for (int k = 0; k < G.nfold; ++k) fold_launch(c, *G.pp, G.fold[k], dfilm, M.dsq, nf);
+      return WR_OK;
+    }
     if (overlap) return issue_overlap(G, step);
     Pipe& pp = *G.pp;
     const hipStream_t sm = pp.stream;
@@ -2602,10 +2797,24 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
         a.n = pc.n;
         G.nmax = std::max(G.nmax, pc.n);
       }
+      G.nfold = 0;
+      if (M.on()) {
+        // An iteration's pieces follow one another on this pipeline, and a group
+        // holds kGroup pieces: the iterations open at any time are consecutive
+        // and at most kGroup, so iteration i takes pass film i % kGroup.  It is
+        // folded after the group that holds its last piece.
+        const auto& groups = pl.per_pipe[pi];
+        for (int m = 0; m < G.gn; ++m) {
+          G.GA.a[m].film = G.pp->mom[grp[m].iter % kGroup];
+          const Piece* next = m + 1 < G.gn ? &grp[m + 1]
+                              : r + 1 < static_cast<int>(groups.size()) ? &groups[r + 1][0] : nullptr;
+          if (!next || next->iter != grp[m].iter) G.fold[G.nfold++] = grp[m].iter % kGroup;
+        }
+      }
       live += G.gn > 0;
     }
     if (!live) continue;
-    if (int rc = issue_round(c, live, nsteps, [&](int pi, int step) {
+    if (int rc = issue_round(c, live, nsteps + (M.on() ? 1 : 0), [&](int pi, int step) {
           return round[pi].gn > 0 ? issue(round[pi], step) : WR_OK;
         }, npl))
       return rc;
@@ -2619,9 +2828,11 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
   // an error after the first launch leaves a caller's device film as it was
   // before the render (its saved copy), not holding a partial render
   auto restore_film = [&](int rc) -> int {
+    if (M.on()) c->mom_dirty = true;  // pass films may hold unfolded work
     if (pooled && film_on_device) {
       (void)hipDeviceSynchronize();  // the pipelines' launches in flight
       (void)hipMemcpy(dfilm, c->film_bak, nf * sizeof(float), hipMemcpyDeviceToDevice);
+      if (M.on()) (void)hipMemcpy(M.dsq, c->film_bak + nf, nf * sizeof(float), hipMemcpyDeviceToDevice);
     }
     return rc;
   };
@@ -2636,12 +2847,19 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     const BdptBuf& B = c->pipes[0].bb[0];
     const int safe = std::min({B.cap_sq / (kVMax + 2), B.vcap / kVMax, B.ccap / kCvMax, cap}) / 64 * 64;
     if (safe < 64) return restore_film(fail(WR_E_HIP, "BDPT pools too small for a 64-path piece"));
-    if (film_on_device) HIPCHK(hipMemcpyAsync(dfilm, c->film_bak, nf * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    else HIPCHK(hipMemsetAsync(dfilm, 0, nf * sizeof(float), c->stream));
+    // (a moments render folds only into the caller's two films, and a finished
+    // run leaves every pass film folded and clear: both films go back alike)
+    if (film_on_device) {
+      HIPCHK(hipMemcpyAsync(dfilm, c->film_bak, nf * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+      if (M.on())
+        HIPCHK(hipMemcpyAsync(M.dsq, c->film_bak + nf, nf * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    } else {
+      HIPCHK(hipMemsetAsync(dfilm, 0, nbak * sizeof(float), c->stream));
+    }
     if (st) *st = st0;
     A0.untiled = 1;
     overflow = 0;
-    if (int rc = run(plan_pieces(f_lo, f_hi, P, 64, safe, fit, c->piece_min))) return restore_film(rc);
+    if (int rc = run(plan_pieces(f_lo, f_hi, P, 64, safe, fit, c->piece_min, M.on()))) return restore_film(rc);
     // (env WR_TEST_REDO_FAIL=1: the test of this error path treats the redo as overflowed)
     if (overflow || std::getenv("WR_TEST_REDO_FAIL"))
       return restore_film(fail(WR_E_HIP, "BDPT pools overflowed with pieces the worst case fits"));
@@ -2651,7 +2869,7 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     for (int i = 0; i < np; ++i) st->work_bytes += static_cast<int64_t>(c->pipes[i].work.cap);
     st->work_paths += static_cast<int64_t>(np) * kGroup * cap;
   }
-  return film_return(c, film, film_on_device, nf);
+  return moments_return(c, film, M, film_on_device, nf);
 }
 
 static int check_vcm(const wr_context* c, const wr_vcm_params* prm, const float* film) {
@@ -2666,7 +2884,8 @@ static int check_vcm(const wr_context* c, const wr_vcm_params* prm, const float*
   if (c->ds.nlights <= 0) return fail(WR_E_SCENE, "VCM needs at least one area light");
   return WR_OK;
 }
-static int render_vcm_one(wr_context* c, const wr_vcm_params* prm, float* film, int film_on_device, wr_stats* st) {
+static int render_vcm_one(wr_context* c, const wr_vcm_params* prm, float* film, int film_on_device, wr_stats* st,
+                          float* film_sq = nullptr) {
   HIPCHK(hipSetDevice(c->device));
   const double t0 = host_now();
   const int P = prm->width * prm->height;
@@ -2682,7 +2901,13 @@ static int render_vcm_one(wr_context* c, const wr_vcm_params* prm, float* film, 
   }
   float* dfilm = nullptr;
   const size_t nf = size_t(P) * 3;
-  if (int rc = film_target(c, film, film_on_device, nf, &dfilm)) return rc;
+  MomentFilms M;
+  M.sq = film_sq;
+  if (int rc = moments_target(c, film, M, film_on_device, nf, &dfilm)) return rc;
+  if (M.on()) {
+    if (int rc = ensure_moments(c, np, nf)) return rc;
+    c->mom_dirty = true;  // until the render has finished
+  }
   begin_render(c, np, prm->time_kernels);
   VcmArgs X0;
   BdptArgs& A0 = X0.a;
@@ -2723,6 +2948,7 @@ static int render_vcm_one(wr_context* c, const wr_vcm_params* prm, float* film, 
       X.a.sc = pp.sc + m;
       const int it = prm->iter_begin + it0 + m;
       X.a.iter = static_cast<uint32_t>(it);
+      if (M.on()) X.a.film = pp.mom[m];  // member m's iteration, folded below
       // runIteration's radius schedule and MIS factors (:50-64), host float
       float radius = base_radius;
       radius /= powf(static_cast<float>(it + 1), 0.5f * (1.f - prm->radius_alpha));
@@ -2792,10 +3018,13 @@ static int render_vcm_one(wr_context* c, const wr_vcm_params* prm, float* film, 
                          nsh);
       tm.mark(WR_K_SHADE);
     }
+    if (M.on())
+      for (int m = 0; m < gn; ++m) fold_launch(c, pp, m, dfilm, M.dsq, nf);
   }
   HIPCHK(hipGetLastError());
   if (int rc = finish_render(c, np, st, t0)) return rc;
-  return film_return(c, film, film_on_device, nf);
+  if (M.on()) c->mom_dirty = false;
+  return moments_return(c, film, M, film_on_device, nf);
 }
 
 static int check_radiance(const wr_context* c, const wr_ray* rays, int64_t n64, int32_t max_depth, const float* rgb) {
@@ -2875,7 +3104,8 @@ static int check_path(const wr_context* c, const wr_path_params* prm, const floa
   if (c->ds.nlights <= 0) return fail(WR_E_SCENE, "path tracing needs at least one area light");
   return WR_OK;
 }
-static int render_path_one(wr_context* c, const wr_path_params* prm, float* film, int film_on_device, wr_stats* st) {
+static int render_path_one(wr_context* c, const wr_path_params* prm, float* film, int film_on_device, wr_stats* st,
+                           float* film_sq = nullptr) {
   HIPCHK(hipSetDevice(c->device));
   const double t0 = host_now();
   const int P = prm->width * prm->height;
@@ -2894,7 +3124,13 @@ static int render_path_one(wr_context* c, const wr_path_params* prm, float* film
   }
   float* dfilm = nullptr;
   const size_t nf = size_t(P) * 3;
-  if (int rc = film_target(c, film, film_on_device, nf, &dfilm)) return rc;
+  MomentFilms M;
+  M.sq = film_sq;
+  if (int rc = moments_target(c, film, M, film_on_device, nf, &dfilm)) return rc;
+  if (M.on()) {
+    if (int rc = ensure_moments(c, np, nf)) return rc;
+    c->mom_dirty = true;  // until the render has finished
+  }
   begin_render(c, np, prm->time_kernels);
   PtArgs A0;
   A0.S = c->ds;
@@ -2922,6 +3158,7 @@ static int render_path_one(wr_context* c, const wr_path_params* prm, float* film
       A[m].ctr = pp.ctr;
       A[m].sc = pp.sc + m;
       A[m].k = static_cast<uint32_t>(gk + m);
+      if (M.on()) A[m].film = pp.mom[m];  // member m's sample, folded below
     }
     HIPCHK(hipMemsetAsync(pp.sc, 0, gn * sizeof(StepCounters), sm));
     hipLaunchKernelGGL(k_pt_gen, dim3(g, gn), dim3(kShadeBlock), 0, sm, GA);
@@ -2949,10 +3186,13 @@ static int render_path_one(wr_context* c, const wr_path_params* prm, float* film
       tm.mark(WR_K_SHADE);
       if (!more) break;
     }
+    if (M.on())
+      for (int m = 0; m < gn; ++m) fold_launch(c, pp, m, dfilm, M.dsq, nf);
   }
   HIPCHK(hipGetLastError());
   if (int rc = finish_render(c, np, st, t0)) return rc;
-  return film_return(c, film, film_on_device, nf);
+  if (M.on()) c->mom_dirty = false;
+  return moments_return(c, film, M, film_on_device, nf);
 }
 
 
@@ -3168,6 +3408,82 @@ int wr_render_path(wr_context* c, const wr_path_params* prm, float* film, int fi
                         q.sample_count = hi - lo;
                         return render_path_one(d, &q, buf, 1, s);
                       });
+}
+
+// ---- moments renders: film += sum of the pass films, film_sq += sum of their squares
+static int check_moments(const wr_context* c, const float* film_sq) {
+  if (!film_sq) return fail(WR_E_ARG, "null argument (film_sq)");
+  if (!c->subs.empty())
+    return fail(WR_E_ARG, "moments renders are not supported on a multi-device context (wr_create_multi): "
+                          "it shares one iteration out over its devices; use one context per device");
+  return WR_OK;
+}
+int wr_render_bdpt_moments(wr_context* c, const wr_bdpt_params* prm, float* film, float* film_sq, int films_on_device,
+                           wr_stats* st) {
+  if (int rc = check_bdpt(c, prm, film)) return rc;
+  if (int rc = check_moments(c, film_sq)) return rc;
+  DeviceGuard dg;
+  const int64_t T = static_cast<int64_t>(prm->iterations) * prm->width * prm->height;
+  return render_bdpt_one(c, prm, 0, T, film, films_on_device, st, film_sq);
+}
+int wr_render_vcm_moments(wr_context* c, const wr_vcm_params* prm, float* film, float* film_sq, int films_on_device,
+                          wr_stats* st) {
+  if (int rc = check_vcm(c, prm, film)) return rc;
+  if (int rc = check_moments(c, film_sq)) return rc;
+  DeviceGuard dg;
+  return render_vcm_one(c, prm, film, films_on_device, st, film_sq);
+}
+int wr_render_path_moments(wr_context* c, const wr_path_params* prm, float* film, float* film_sq, int films_on_device,
+                           wr_stats* st) {
+  if (int rc = check_path(c, prm, film)) return rc;
+  if (int rc = check_moments(c, film_sq)) return rc;
+  DeviceGuard dg;
+  return render_path_one(c, prm, film, films_on_device, st, film_sq);
+}
+
+int wr_film_error(wr_context* c, const float* film, const float* film_sq, int width, int height, int n_passes,
+                  int films_on_device, float* stderr_map, wr_error_info* out) {
+  if (!film || !film_sq || !out) return fail(WR_E_ARG, "null argument");
+  if (width <= 0 || height <= 0) return fail(WR_E_ARG, "bad film size");
+  if (n_passes < 2) return fail(WR_E_ARG, "a standard error needs at least 2 passes");
+  if (films_on_device && !c) return fail(WR_E_ARG, "device films need a context");
+  const size_t nf = size_t(width) * height * 3;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  if (!films_on_device) {  // the same formulas on the CPU; needs no device
+    const double np = static_cast<double>(n_passes);
+    for (size_t i = 0; i < nf; ++i) {
+      double mu, se;
+      film_error_value(film[i], film_sq[i], np, &mu, &se);
+      if (stderr_map) stderr_map[i] = static_cast<float>(se);
+      acc[0] += se;
+      acc[1] += mu;
+      if (mu > 0.0) {
+        acc[2] = std::max(acc[2], se / mu);
+        acc[3] += 1.0;
+      }
+    }
+  } else {
+    DeviceGuard dg;
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->err_acc) HIPCHK(hipMalloc(&c->err_acc, sizeof acc));
+    // after the caller's work on the legacy null stream, like a render
+    (void)hipEventRecord(c->t_null, nullptr);
+    (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
+    HIPCHK(hipMemsetAsync(c->err_acc, 0, sizeof acc, c->stream));
+    const size_t blocks = (nf + kErrBlock - 1) / kErrBlock;
+    const int g = static_cast<int>(std::max<size_t>(1, std::min<size_t>(blocks, size_t(c->cus) * 8)));
+    hipLaunchKernelGGL(k_film_error, dim3(g), dim3(kErrBlock), 0, c->stream, film, film_sq, nf, n_passes, stderr_map,
+                       c->err_acc);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(acc, c->err_acc, sizeof acc, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  out->sum_stderr = acc[0];
+  out->sum_mean = acc[1];
+  out->rel_stderr = acc[1] > 0.0 ? acc[0] / acc[1] : 0.0;
+  out->max_rel_stderr = acc[2];
+  out->values = static_cast<int64_t>(acc[3]);
+  return WR_OK;
 }
 
 int wr_path_radiance(wr_context* c, const wr_ray* rays, int64_t n64, int32_t max_depth, uint32_t seed,

@@ -25,7 +25,8 @@ EXPORTS = ["wr_scene_load", "wr_scene_from_desc", "wr_scene_info_get", "wr_scene
            "wr_comm_init", "wr_comm_info", "wr_film_reduce", "wr_set_pipelines", "wr_set_trace_mode", "wr_trace_closest", "wr_occluded",
            "wr_render_bdpt", "wr_render_path", "wr_render_vcm", "wr_path_radiance", "wr_film_write_ppm",
            "wr_film_write_image", "wr_checkpoint_save", "wr_checkpoint_load", "wr_last_error", "wr_api_version",
-           "wr_reserve", "wr_request_hw_queues"]
+           "wr_reserve", "wr_request_hw_queues", "wr_render_bdpt_moments", "wr_render_vcm_moments",
+           "wr_render_path_moments", "wr_film_error"]
 CKPT_BDPT, CKPT_VCM, CKPT_PT = 1, 2, 3
 
 
@@ -95,6 +96,15 @@ class WrStats(C.Structure):
         d["kernel_ms"] = list(self.kernel_ms)
         d["kernel_launches"] = list(self.kernel_launches)
         return d
+
+
+class WrErrorInfo(C.Structure):
+    """wr_error_info: what wr_film_error reduces from the two films of a moments render."""
+    _fields_ = [("sum_stderr", C.c_double), ("sum_mean", C.c_double), ("rel_stderr", C.c_double),
+                ("max_rel_stderr", C.c_double), ("values", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class WrError(RuntimeError):
@@ -187,6 +197,10 @@ def lib():
                                        C.POINTER(WrStats)]
         L.wr_film_write_ppm.argtypes = [C.POINTER(C.c_float), I, I, C.c_float, C.c_float, I, C.c_char_p]
         L.wr_film_write_image.argtypes = [C.POINTER(C.c_float), I, I, C.c_float, C.c_float, I, C.c_char_p]
+        L.wr_render_bdpt_moments.argtypes = [P, C.POINTER(WrBdptParams), P, P, I, C.POINTER(WrStats)]
+        L.wr_render_vcm_moments.argtypes = [P, C.POINTER(WrVcmParams), P, P, I, C.POINTER(WrStats)]
+        L.wr_render_path_moments.argtypes = [P, C.POINTER(WrPathParams), P, P, I, C.POINTER(WrStats)]
+        L.wr_film_error.argtypes = [P, P, P, I, I, I, I, P, C.POINTER(WrErrorInfo)]
         L.wr_last_error.restype = C.c_char_p
         _lib = L
     return _lib
@@ -447,6 +461,74 @@ class Context:
         film = _host_film(film, height, width)
         check(lib().wr_render_path(self.h, C.byref(p), film.ctypes.data_as(C.c_void_p), 0, C.byref(st)))
         return film, st
+
+    def _moments(self, fn, p, width, height, film, film_sq, film_ptr, film_sq_ptr):
+        """The two films of a moments render: host arrays (made when None,
+        accumulated into otherwise) or, with both pointers given, device films."""
+        st = WrStats()
+        if (film_ptr is None) != (film_sq_ptr is None):
+            raise ValueError("film_ptr and film_sq_ptr go together: both films live in the same memory space")
+        if film_ptr is not None:
+            check(fn(self.h, C.byref(p), C.c_void_p(film_ptr), C.c_void_p(film_sq_ptr), 1, C.byref(st)))
+            return None, None, st
+        film = _host_film(film, height, width)
+        film_sq = _host_film(film_sq, height, width)
+        check(fn(self.h, C.byref(p), film.ctypes.data_as(C.c_void_p), film_sq.ctypes.data_as(C.c_void_p), 0,
+                 C.byref(st)))
+        return film, film_sq, st
+
+    def render_bdpt_moments(self, width, height, iterations=1, seed=5489, iter_begin=0, control_length=3,
+                            max_path_length=10, faithful=1, time_kernels=0, count_work=0, film=None, film_sq=None,
+                            film_ptr=None, film_sq_ptr=None):
+        """wr_render_bdpt_moments: film += the iterations' films (what render_bdpt
+        adds), film_sq += their squares per value.  Returns (film, film_sq, stats)."""
+        p = WrBdptParams(width, height, iterations, iter_begin, control_length, max_path_length, seed,
+                         faithful, time_kernels, count_work)
+        return self._moments(lib().wr_render_bdpt_moments, p, width, height, film, film_sq, film_ptr, film_sq_ptr)
+
+    def render_vcm_moments(self, width, height, iterations=1, seed=5489, iter_begin=0, min_path_length=0,
+                           max_path_length=10, radius_factor=0.003, radius_alpha=0.75, time_kernels=0, count_work=0,
+                           film=None, film_sq=None, film_ptr=None, film_sq_ptr=None):
+        """wr_render_vcm_moments.  Films as render_bdpt_moments."""
+        p = WrVcmParams(width, height, iterations, iter_begin, min_path_length, max_path_length, radius_factor,
+                        radius_alpha, seed, time_kernels, count_work)
+        return self._moments(lib().wr_render_vcm_moments, p, width, height, film, film_sq, film_ptr, film_sq_ptr)
+
+    def render_path_moments(self, width, height, spp, max_depth=7, seed=5489, sample_begin=0, sample_count=0,
+                            time_kernels=0, count_work=0, film=None, film_sq=None, film_ptr=None, film_sq_ptr=None):
+        """wr_render_path_moments: a pass is one sample index of the spp grid
+        (strata, not i.i.d.: the error estimate from film_sq is conservative)."""
+        p = WrPathParams(width, height, spp, max_depth, sample_begin, sample_count, seed, time_kernels,
+                         count_work)
+        return self._moments(lib().wr_render_path_moments, p, width, height, film, film_sq, film_ptr, film_sq_ptr)
+
+    def film_error(self, film_ptr, film_sq_ptr, width, height, n_passes, stderr_map_ptr=None):
+        """wr_film_error on device films of this context (pointers, e.g. torch
+        data_ptr()); stderr_map_ptr: a device film that receives the map."""
+        info = WrErrorInfo()
+        check(lib().wr_film_error(self.h, C.c_void_p(film_ptr), C.c_void_p(film_sq_ptr), width, height, n_passes, 1,
+                                  C.c_void_p(stderr_map_ptr) if stderr_map_ptr is not None else None,
+                                  C.byref(info)))
+        return info
+
+
+def film_error(film, film_sq, n_passes, stderr_map=False):
+    """wr_film_error on host films ((height, width, 3) float32 sums of n_passes
+    passes and of their squares): the standard error of the mean image, on the
+    CPU, no device needed.  Returns WrErrorInfo, or (WrErrorInfo, map) with
+    stderr_map=True."""
+    film = np.ascontiguousarray(film, np.float32)
+    film_sq = np.ascontiguousarray(film_sq, np.float32)
+    if film.ndim != 3 or film.shape[2] != 3 or film_sq.shape != film.shape:
+        raise ValueError(f"film and film_sq must both have shape (height, width, 3), got {film.shape} and "
+                         f"{film_sq.shape}")
+    h, w = film.shape[:2]
+    out = np.zeros_like(film) if stderr_map else None
+    info = WrErrorInfo()
+    check(lib().wr_film_error(None, film.ctypes.data_as(C.c_void_p), film_sq.ctypes.data_as(C.c_void_p), w, h,
+                              int(n_passes), 0, out.ctypes.data_as(C.c_void_p) if stderr_map else None,
+                              C.byref(info)))
+    return (info, out) if stderr_map else info
 
 
 def comm_unique_id():
