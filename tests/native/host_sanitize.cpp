@@ -2,7 +2,8 @@
 // the product's host translation units -- the in-place .scene/.obj loader and
 // the threaded KD build (wr_scene.cpp, the reference's scene.cpp:259-489 and
 // KDtreeAccel.cpp:12-307), the threaded verified-BVH build (wr_bvh.cpp), the
-// image writers (wr_image.cpp) and the film checkpoint (wr_checkpoint.cpp) --
+// flattening into the device layout (wr_flatten.cpp), the image writers
+// (wr_image.cpp) and the film checkpoint (wr_checkpoint.cpp) --
 // on the scenes and malformed inputs named on the command line.  Built by
 // tests/test_sanitize.py twice: -fsanitize=address,undefined and
 // -fsanitize=thread.  CPU only; no HIP code is compiled in.
@@ -20,6 +21,7 @@
 
 #include "winmad_rt.h"
 #include "wr_bvh.h"
+#include "wr_flatten.h"
 #include "wr_scene.h"
 
 static int fail(const std::string& m) {
@@ -148,10 +150,12 @@ int main(int argc, char** argv) {
     const uint64_t fp = wr::scene_fingerprint(s);
     wrf::FastHost f;
     if (!s.prims.empty() && !s.lights.empty()) wrf::build_fast(s, f);
+    wr::SceneFlat flat;
+    if (!s.prims.empty()) wr::flatten_scene(s, flat);  // as wr_create: a scene without primitives is refused first
     if (int rc = from_arrays(s)) return rc;
-    std::printf("%s: %zu prims, %zu kd nodes, dump %zu B, fp %016llx, bvh %s (%zu nodes)\n", path, s.prims.size(),
-                s.nodes.size(), dump.size(), static_cast<unsigned long long>(fp), f.ok ? "ok" : f.why.c_str(),
-                f.nodes.size());
+    std::printf("%s: %zu prims, %zu kd nodes, dump %zu B, fp %016llx, bvh %s (%zu nodes), flat %zu refs\n", path,
+                s.prims.size(), s.nodes.size(), dump.size(), static_cast<unsigned long long>(fp),
+                f.ok ? "ok" : f.why.c_str(), f.nodes.size(), flat.ref_a.size());
   }
   std::printf("DONE\n");
   return 0;

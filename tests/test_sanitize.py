@@ -4,7 +4,8 @@ r3 item 9), CPU only.
 tests/native/host_sanitize.cpp drives the product's host translation units --
 the in-place .scene/.obj loader and the threaded KD build (wr_scene.cpp; the
 reference's scene.cpp:259-489, tiny_obj_loader.cpp:461-661 semantics and
-KDtreeAccel.cpp:12-307), the threaded verified-BVH build (wr_bvh.cpp), the image
+KDtreeAccel.cpp:12-307), the threaded verified-BVH build (wr_bvh.cpp), the
+flattening into the device layout (wr_flatten.cpp), the image
 writers (wr_image.cpp) and the checkpoint (wr_checkpoint.cpp) -- over the
 reference scenes, a synthetic torus large enough for both builders to spawn
 helper threads, and malformed inputs.  Two builds: AddressSanitizer +
@@ -22,7 +23,7 @@ from winmad_rt import scenes
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "winmad-s-raytracer-v1.0_amd", "csrc")
-SRCS = ["wr_scene.cpp", "wr_bvh.cpp", "wr_image.cpp", "wr_checkpoint.cpp"]
+SRCS = ["wr_scene.cpp", "wr_bvh.cpp", "wr_flatten.cpp", "wr_image.cpp", "wr_checkpoint.cpp"]
 FLAGS = {
     "asan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-O1", "-g"],
     "tsan": ["-fsanitize=thread", "-fno-omit-frame-pointer", "-O1", "-g"],

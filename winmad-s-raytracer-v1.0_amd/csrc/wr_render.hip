@@ -24,15 +24,19 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <memory>
 #include <string>
 #include <thread>
 #include <type_traits>
 #include <vector>
 
 #include "winmad_rt.h"
+#include "wr_flatten.h"
 #include "wr_scene.h"
 #include "wr_traverse.h"
 #include "wr_fast.h"
@@ -501,31 +505,76 @@ struct wr_scene {
   wr::Scene s;
 };
 
+// wr_flatten.h's plain element types are uploaded as the kernels' (DevScene)
+static_assert(sizeof(wr::U2) == sizeof(uint2) && alignof(wr::U2) == alignof(uint2) && offsetof(wr::U2, y) == 4, "U2 is uint2");
+static_assert(sizeof(wr::U4) == sizeof(uint4) && alignof(wr::U4) == alignof(uint4) && offsetof(wr::U4, w) == 12, "U4 is uint4");
+static_assert(sizeof(wr::F2) == sizeof(float2) && alignof(wr::F2) == alignof(float2) && offsetof(wr::F2, y) == 4, "F2 is float2");
+static_assert(sizeof(wr::F4) == sizeof(float4) && alignof(wr::F4) == alignof(float4) && offsetof(wr::F4, w) == 12, "F4 is float4");
+static_assert(sizeof(wr::F3) == sizeof(V3), "F3 is V3");
+static_assert(sizeof(wr::Light) == sizeof(DLight) && offsetof(wr::Light, p0) == offsetof(DLight, p0) &&
+                  offsetof(wr::Light, d1) == offsetof(DLight, d1) && offsetof(wr::Light, d2) == offsetof(DLight, d2) &&
+                  offsetof(wr::Light, fx) == offsetof(DLight, fx) && offsetof(wr::Light, fy) == offsetof(DLight, fy) &&
+                  offsetof(wr::Light, fz) == offsetof(DLight, fz) && offsetof(wr::Light, le) == offsetof(DLight, le) &&
+                  offsetof(wr::Light, inv_area) == offsetof(DLight, inv_area),
+              "Light is DLight");
+static_assert(sizeof(wr::Material) == sizeof(DMat) && offsetof(wr::Material, diffuse) == offsetof(DMat, diffuse) &&
+                  offsetof(wr::Material, phong) == offsetof(DMat, phong) &&
+                  offsetof(wr::Material, specular) == offsetof(DMat, specular) &&
+                  offsetof(wr::Material, phong_exp) == offsetof(DMat, phong_exp) &&
+                  offsetof(wr::Material, index) == offsetof(DMat, index),
+              "Material is DMat");
+
 namespace {
+// Grow-only device buffer of n elements, move-only.  The owner's device must be
+// current when it grows and when it dies (wr_destroy selects it before `delete`).
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t n = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p, o.p), std::swap(n, o.n);
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  // at least `want` elements; a block that is too small is freed and replaced
+  // (its contents are gone).  On failure the buffer is {nullptr, 0}.
+  int grow(size_t want) {
+    if (p && n >= want) return WR_OK;
+    release();
+    const hipError_t e = hipMalloc(&p, want * sizeof(T));
+    if (e != hipSuccess) {
+      p = nullptr;
+      return fail(WR_E_HIP, "hipMalloc of " + std::to_string(want * sizeof(T)) + " bytes: " + hipGetErrorString(e));
+    }
+    n = want;
+    return WR_OK;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr, n = 0;
+  }
+};
+
 // Device memory arena: bump allocation out of one hipMalloc per arena.
 struct Arena {
-  char* base = nullptr;
-  size_t cap = 0, used = 0;
-  int reserve(size_t bytes) {
+  DevBuf<char> mem;
+  size_t used = 0;
+  size_t cap() const { return mem.n; }
+  int reserve(size_t bytes) {  // a fresh block, whatever was there
     release();
-    if (hipMalloc(&base, bytes) != hipSuccess) {
-      base = nullptr;
-      return fail(WR_E_HIP, "hipMalloc of " + std::to_string(bytes) + " bytes failed");
-    }
-    cap = bytes;
-    used = 0;
-    return WR_OK;
+    return mem.grow(bytes);
   }
   template <class T>
   T* take(size_t n) {
     size_t off = (used + 255) & ~size_t(255);
     used = off + n * sizeof(T);
-    return reinterpret_cast<T*>(base + off);
+    return reinterpret_cast<T*>(mem.p + off);
   }
   void release() {
-    if (base) (void)hipFree(base);
-    base = nullptr;
-    cap = used = 0;
+    mem.release();
+    used = 0;
   }
 };
 
@@ -535,6 +584,42 @@ size_t measure(Fn fn) {  // bytes an arena layout needs
   fn(a);
   return a.used + 256;
 }
+
+// One arena upload: every array is named once, with the pointer it lands in.
+// commit() lays the arrays out in the order they were added (256-byte aligned,
+// as Arena::take), reserves the arena, copies and assigns.
+struct Upload {
+  struct Item {
+    const void* src;
+    size_t bytes, room;  // bytes copied, bytes taken (>= bytes)
+    std::function<void(char*)> assign;
+  };
+  std::vector<Item> items;
+  // `min_elems`: elements of room to take when the vector holds fewer
+  template <class D, class S>
+  void add(D** slot, const std::vector<S>& v, size_t min_elems = 0) {
+    items.push_back({v.data(), v.size() * sizeof(S), std::max(v.size(), min_elems) * sizeof(S),
+                     [slot](char* p) { *slot = reinterpret_cast<D*>(p); }});
+  }
+  template <class D>
+  void room(D** slot, size_t n) {  // n elements nothing is copied to
+    items.push_back({nullptr, 0, n * sizeof(D), [slot](char* p) { *slot = reinterpret_cast<D*>(p); }});
+  }
+  int commit(Arena& A, const char* what) {
+    const size_t total = measure([&](Arena& a) {
+      for (const Item& it : items) a.take<char>(it.room);
+    });
+    if (int rc = A.reserve(total)) return rc;
+    for (const Item& it : items) {
+      char* dst = A.take<char>(it.room);
+      it.assign(dst);
+      if (!it.bytes) continue;
+      const hipError_t e = hipMemcpy(dst, it.src, it.bytes, hipMemcpyHostToDevice);
+      if (e != hipSuccess) return fail(WR_E_HIP, std::string(what) + " upload: " + hipGetErrorString(e));
+    }
+    return WR_OK;
+  }
+};
 }  // namespace
 
 // One render pipeline: a HIP stream with its own work buffers and queue
@@ -552,6 +637,7 @@ constexpr int kMaxPipes = WR_MAX_PIPES;
 // launch tail (its slowest ray) is paid once per group.
 struct Pipe {
   hipStream_t stream = nullptr;
+  bool own_stream = false;  // pipeline 0 runs on the context stream, which the context destroys
   DevCounters* ctr = nullptr;
   StepCounters* sc = nullptr;  // [kGroup]
   Arena work;
@@ -562,9 +648,8 @@ struct Pipe {
   BdptBuf bb[kGroup]{};
   PtBuf pb[kGroup]{};
   VcmBuf vb[kGroup]{};
-  float* t2buf = nullptr;  // WR_TRACE_BVH: per-ray t2 of the BVH search (launch index)
-  int2* spill = nullptr;   // WR_TRACE_BVH: the search stack's spill area (fast_blocks x 64 lanes)
-  size_t t2_cap = 0;
+  DevBuf<float> t2buf;  // WR_TRACE_BVH: 5 floats per ray of a launch: per-ray t2 of the BVH search, lists (TraceSlot)
+  DevBuf<int2> spill;   // WR_TRACE_BVH: the search stack's spill area (fast_blocks x 64 lanes)
   std::vector<hipEvent_t> events;  // Timer marks (time_kernels)
   std::vector<int> ev_cat;
   size_t ev_used = 0;
@@ -578,8 +663,17 @@ struct Pipe {
   uint8_t* delayed = nullptr;            // [kGroup][late_paths]
   // moments renders only (wr_render_*_moments): the films of the passes this
   // pipeline has open, zero between passes (k_film_fold clears what it folds)
-  float* mom[kGroup]{};
-  size_t mom_n = 0;  // floats each
+  DevBuf<float> mom[kGroup];
+  Pipe() = default;
+  Pipe(const Pipe&) = delete;
+  Pipe& operator=(const Pipe&) = delete;
+  ~Pipe() {  // with the context's device current and the streams idle (wr_destroy)
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    if (done) (void)hipEventDestroy(done);
+    if (ctr) (void)hipFree(ctr);
+    if (sc) (void)hipFree(sc);
+    if (stream && own_stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 struct wr_context {
@@ -595,15 +689,12 @@ struct wr_context {
   Arena scene_mem;
   int64_t scene_bytes = 0;
   DevCounters* ctr = nullptr;  // API traversal
-  float* film_tmp = nullptr;
-  size_t film_tmp_n = 0;
-  float* film_bak = nullptr;  // a device film as it was before a BDPT render (redone on pool overflow)
-  size_t film_bak_n = 0;
+  DevBuf<float> film_tmp;  // a host film's device copy
+  DevBuf<float> film_bak;  // a device film as it was before a BDPT render (redone on pool overflow)
   bool mom_dirty = false;  // a moments render failed under way: its pass films are cleared before the next
-  double* err_acc = nullptr;  // wr_film_error on device films: sum se, sum mu, max se / mu (bits), values
+  DevBuf<double> err_acc;  // wr_film_error on device films: sum se, sum mu, max se / mu (bits), values
   DevCounters* host_ctr = nullptr;  // pinned: the pipelines' counters after a render (finish_render)
-  char* api_tmp = nullptr;  // wr_trace_closest / wr_occluded / wr_path_radiance scratch, grown on demand
-  size_t api_tmp_n = 0;
+  DevBuf<char> api_tmp;  // wr_trace_closest / wr_occluded / wr_path_radiance scratch, grown on demand
   int grid = 2048;
   int cus = 256;
   int nmats = 0, has_sph = 0;  // entries of ds.mats; the scene has a sphere (BdptArgs)
@@ -660,21 +751,30 @@ struct wr_context {
   int defer = -1;
   // BDPT light and camera passes overlapped (wr_bdpt.h; env WR_BDPT_OVERLAP=0: sequential)
   bool bdpt_overlap = true;
-  float* api_t2 = nullptr;  // t2 scratch of the API path
-  size_t api_t2_cap = 0;
-  int2* api_spill = nullptr;  // the API path's search stack spill area
+  DevBuf<float> api_t2;    // t2 scratch of the API path (5 floats per ray, as Pipe::t2buf)
+  DevBuf<int2> api_spill;  // the API path's search stack spill area
   // ---- several GPUs (wr_create_multi): this context drives devices[0], `subs`
   // the others; work is dealt to all of them and their films are summed on
   // devices[0] (RCCL reduce over xGMI when the devices are distinct)
   std::vector<wr_context*> subs;
   std::vector<ncclComm_t> dev_comms;  // one per device (ncclCommInitAll), empty: peer copies
-  float* red_buf = nullptr;  // this device's film of a multi-device render
-  size_t red_n = 0;
-  float* stage_buf = nullptr;  // devices[0]: a peer film copied in before it is added
-  size_t stage_n = 0;
+  DevBuf<float> red_buf;    // this device's film of a multi-device render
+  DevBuf<float> stage_buf;  // devices[0]: a peer film copied in before it is added
   // ---- one process per GPU (wr_comm_init): this rank's communicator
   ncclComm_t comm = nullptr;
   int comm_ranks = 0, comm_rank = 0;
+  wr_context() = default;
+  wr_context(const wr_context&) = delete;
+  wr_context& operator=(const wr_context&) = delete;
+  // Only wr_destroy deletes a context: it ends the sub-contexts and
+  // communicators, selects `device` and idles the streams first.  The members
+  // (pipelines, arenas, buffers) then free themselves.
+  ~wr_context() {
+    if (t_ref) (void)hipEventDestroy(t_ref);
+    if (t_null) (void)hipEventDestroy(t_null);
+    if (host_ctr) (void)hipHostFree(host_ctr);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 namespace {
@@ -1040,7 +1140,7 @@ int pipelines_that_fit(wr_context* c, int kind, int P, int sets, int want) {
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return want;
   size_t held = 0;
-  for (int i = 0; i < kMaxPipes; ++i) held += c->pipes[i].work.cap;
+  for (int i = 0; i < kMaxPipes; ++i) held += c->pipes[i].work.cap();
   const size_t budget = (free_b + held) / 4 * 3;
   const int fit = static_cast<int>(std::min<size_t>(static_cast<size_t>(want), std::max<size_t>(1, budget / per)));
   for (int i = fit; i < kMaxPipes; ++i) {  // memory-limited: free the rest
@@ -1165,7 +1265,7 @@ struct TraceSlot {
   int* rlist_n;   // rays the search left to k_fast_resolve (their list: the t2 region)
 };
 TraceSlot tslot(Pipe& p, int slot) {
-  return TraceSlot{&p.sc[0].fetch[slot], p.t2buf, p.t2_cap, &p.sc[0].hard[slot][0], p.spill, &p.sc[0].rlist[slot]};
+  return TraceSlot{&p.sc[0].fetch[slot], p.t2buf.p, p.t2buf.n / 5, &p.sc[0].hard[slot][0], p.spill.p, &p.sc[0].rlist[slot]};
 }
 // t2 scratch + hard-ray list of a pipeline for launches of up to `rays` rays
 // search-stack spill entries per lane: the larger of the context's trees
@@ -1190,15 +1290,9 @@ FastScene search_scene(const wr_context* c) {
 }
 int ensure_t2(wr_context* c, Pipe& p, size_t rays) {
   if (!c->fast_on) return WR_OK;
-  if (!p.spill && max_spill_entries(c) > 0)
-    HIPCHK(hipMalloc(&p.spill, max_spill_entries(c) * size_t(c->fast_blocks) * 64 * sizeof(int2)));
-  if (p.t2_cap >= rays) return WR_OK;
-  if (p.t2buf) (void)hipFree(p.t2buf);
-  p.t2buf = nullptr;
-  p.t2_cap = 0;
-  HIPCHK(hipMalloc(&p.t2buf, 5 * rays * sizeof(float)));  // t2 / list, hard lists, pair records (int2), pair list
-  p.t2_cap = rays;
-  return WR_OK;
+  if (!p.spill.p && max_spill_entries(c) > 0)
+    if (int rc = p.spill.grow(max_spill_entries(c) * size_t(c->fast_blocks) * 64)) return rc;
+  return p.t2buf.grow(5 * rays);  // t2 / list, hard lists, pair records (int2), pair list
 }
 
 // Late lists of a pipeline (deferred hard rays), `recs` records each, for
@@ -1747,242 +1841,133 @@ int wr_device_count(void) {
   return n;
 }
 
-int wr_create(const wr_scene* sc, int device, wr_context** out) {
-  if (!sc || !out) return fail(WR_E_ARG, "null argument");
-  *out = nullptr;
-  latch_hw_queues();  // before the library's first HIP call: the value HIP reads
-  if (int rc = check_device()) return rc;
-  DeviceGuard dg;
-  const wr::Scene& s = sc->s;
+// ---- wr_create, step by step.  A context under construction is held by a
+// ContextPtr, so every early return ends it the way wr_destroy does.
+struct ContextDelete {
+  void operator()(wr_context* c) const { wr_destroy(c); }
+};
+using ContextPtr = std::unique_ptr<wr_context, ContextDelete>;
+
+static int check_scene(const wr::Scene& s) {
   if (s.prims.empty()) return fail(WR_E_SCENE, "scene has no primitives");
   for (const auto& p : s.prims)  // the reference would index materials[] out of range
     if (p.mat >= static_cast<int>(s.mats.size()))
       return fail(WR_E_SCENE, "primitive material id " + std::to_string(p.mat) + " has no <material>");
-  HIPCHK(hipSetDevice(device));
-  auto* c = new wr_context();
-  c->device = device;
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&c->t_ref, ev_flags(hipEventDefault)) != hipSuccess ||
-      hipEventCreateWithFlags(&c->t_null, ev_flags(hipEventDisableTiming)) != hipSuccess) {
-    wr_destroy(c);
+  return WR_OK;
+}
+
+// streams, events and the pipelines' counters; the device's CU count
+static int make_streams(wr_context& c) {
+  if (hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&c.t_ref, ev_flags(hipEventDefault)) != hipSuccess ||
+      hipEventCreateWithFlags(&c.t_null, ev_flags(hipEventDisableTiming)) != hipSuccess)
     return fail(WR_E_HIP, "hipStreamCreate failed");
-  }
   // Pipeline 0 runs on the context stream: with GPU_MAX_HW_QUEUES = 4 (HIP's
   // default) a fifth stream would share a hardware queue with another and
   // serialize behind it (measured: 4 pipelines 648 Mrays/s on 5 streams, 734 on 4).
-  for (Pipe& pp : c->pipes) {
-    if (&pp == &c->pipes[0]) {
-      pp.stream = c->stream;
-      if (hipEventCreateWithFlags(&pp.done, ev_flags(hipEventDisableTiming)) != hipSuccess ||
-          hipMalloc(&pp.ctr, sizeof(DevCounters)) != hipSuccess ||
-          hipMalloc(&pp.sc, kGroup * sizeof(StepCounters)) != hipSuccess) {
-        wr_destroy(c);
-        return fail(WR_E_HIP, "pipeline stream / counters");
-      }
-      continue;
-    }
-    if (hipStreamCreateWithFlags(&pp.stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&pp.done, ev_flags(hipEventDisableTiming)) != hipSuccess ||
+  for (Pipe& pp : c.pipes) {
+    if (&pp == &c.pipes[0]) pp.stream = c.stream;
+    else if (hipStreamCreateWithFlags(&pp.stream, hipStreamNonBlocking) == hipSuccess) pp.own_stream = true;
+    if (!pp.stream || hipEventCreateWithFlags(&pp.done, ev_flags(hipEventDisableTiming)) != hipSuccess ||
         hipMalloc(&pp.ctr, sizeof(DevCounters)) != hipSuccess ||
-        hipMalloc(&pp.sc, kGroup * sizeof(StepCounters)) != hipSuccess) {
-      wr_destroy(c);
+        hipMalloc(&pp.sc, kGroup * sizeof(StepCounters)) != hipSuccess)
       return fail(WR_E_HIP, "pipeline stream / counters");
-    }
   }
+  hipDeviceProp_t prop;
+  const int cus = hipGetDeviceProperties(&prop, c.device) == hipSuccess ? prop.multiProcessorCount : 0;
+  c.cus = cus > 0 ? cus : 256;
+  return WR_OK;
+}
+
+// The knobs a context reads from the environment when it is created
+// ("Runtime configuration").  Those whose effect depends on the
+// scene's trees are read by read_scene_knobs.
+static void read_knobs(wr_context& c) {
   // one pipeline per hardware queue of this process (HIP's GPU_MAX_HW_QUEUES,
   // default 4; pipeline 0 shares the context stream), at most 16: streams that
   // share a hardware queue serialize behind each other
-  c->npipes = std::max(1, std::min(kMaxPipes, latch_hw_queues()));
-  if (const char* e = std::getenv("WR_PIPES")) c->npipes = std::max(1, std::min(kMaxPipes, std::atoi(e)));
-  if (const char* e = std::getenv("WR_PIECE_CAP")) c->piece_cap = std::max(64, std::atoi(e));
-  if (const char* e = std::getenv("WR_PIECE_MIN")) c->piece_min = std::max(1, std::atoi(e));
-  if (const char* e = std::getenv("WR_TIE_WAVE_MAX")) c->tie_wave_max = std::max(0, std::atoi(e));
-  if (const char* e = std::getenv("WR_SCAN_WAVES")) c->scan_waves = std::max(1, std::atoi(e));
-  if (const char* e = std::getenv("WR_ISSUE_THREADS")) c->issue_threads = std::max(1, std::min(kMaxPipes, std::atoi(e)));
-  if (const char* e = std::getenv("WR_DEFER")) c->defer = std::atoi(e) != 0 ? 1 : 0;
-  if (const char* e = std::getenv("WR_BDPT_OVERLAP")) c->bdpt_overlap = std::atoi(e) != 0;
-  if (const char* e = std::getenv("WR_RESOLVE_GRID")) c->resolve_blocks = std::max(0, std::atoi(e));  // per CU; scaled below
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
-    // grid-stride vertex / resolve kernels: blocks per CU (knob WR_SHADE_GRID).
-    // 2 = one resident round of both group members at 4 waves/SIMD; measured
-    // against 8: C2 +0.9 %, C3 +1.9 %, VCM +1.3 % (16 and 32 lose 1-2 %).
-    // With the path state in records (round 3) 1 does better again: C2 20 it.
-    // +2.0 %, 256 it. +2.7 %, C4 +2.6 %, VCM +3 %, C3 -0.4 % (profiles/r3/shade_grid)
-    int per_cu = 1;
-    if (const char* e = std::getenv("WR_SHADE_GRID")) per_cu = std::max(1, std::min(64, std::atoi(e)));
-    c->grid = std::max(256, prop.multiProcessorCount * per_cu);
-  }
+  c.npipes = std::max(1, std::min(kMaxPipes, latch_hw_queues()));
+  if (const char* e = std::getenv("WR_PIPES")) c.npipes = std::max(1, std::min(kMaxPipes, std::atoi(e)));
+  if (const char* e = std::getenv("WR_PIECE_CAP")) c.piece_cap = std::max(64, std::atoi(e));
+  if (const char* e = std::getenv("WR_PIECE_MIN")) c.piece_min = std::max(1, std::atoi(e));
+  if (const char* e = std::getenv("WR_TIE_WAVE_MAX")) c.tie_wave_max = std::max(0, std::atoi(e));
+  if (const char* e = std::getenv("WR_SCAN_WAVES")) c.scan_waves = std::max(1, std::atoi(e));
+  if (const char* e = std::getenv("WR_ISSUE_THREADS")) c.issue_threads = std::max(1, std::min(kMaxPipes, std::atoi(e)));
+  if (const char* e = std::getenv("WR_DEFER")) c.defer = std::atoi(e) != 0 ? 1 : 0;
+  if (const char* e = std::getenv("WR_BDPT_OVERLAP")) c.bdpt_overlap = std::atoi(e) != 0;
+  // k_fast_resolve's grid, given in blocks per CU
+  if (const char* e = std::getenv("WR_RESOLVE_GRID")) c.resolve_blocks = std::max(0, std::atoi(e)) * c.cus;
+  if (const char* e = std::getenv("WR_RESOLVE_LIST")) c.resolve_list = std::atoi(e) != 0;
+  if (const char* e = std::getenv("WR_BVH_WIDE_LAT")) c.lat_wide = std::atoi(e) != 0;
+  // grid-stride vertex / resolve kernels: blocks per CU (knob WR_SHADE_GRID).
+  // 2 = one resident round of both group members at 4 waves/SIMD; measured
+  // against 8: C2 +0.9 %, C3 +1.9 %, VCM +1.3 % (16 and 32 lose 1-2 %).
+  // With the path state in records (round 3) 1 does better again: C2 20 it.
+  // +2.0 %, 256 it. +2.7 %, C4 +2.6 %, VCM +3 %, C3 -0.4 % (profiles/r3/shade_grid)
+  int per_cu = 1;
+  if (const char* e = std::getenv("WR_SHADE_GRID")) per_cu = std::max(1, std::min(64, std::atoi(e)));
+  c.grid = std::max(256, c.cus * per_cu);
+  if (const char* e = std::getenv("WR_TRACE_STAMPS")) c.stamps = std::atoi(e) != 0;  // triangle scenes only (upload_scene)
+  if (const char* e = std::getenv("WR_TRACE_LOG")) c.trace_log = std::atoi(e) != 0;
+  if (const char* e = std::getenv("WR_TRACE_DENSE")) c.api_dense = std::atoi(e) != 0;
+  if (const char* e = std::getenv("WR_TRACE_NO_CUT")) c.no_cut = std::atoi(e) != 0;
+  if (const char* e = std::getenv("WR_VCM_CELL")) c.vcm_cell = std::min(8.f, std::max(0.25f, (float)std::atof(e)));
+}
 
-  // ---- flatten the tree + primitives into the HBM layout of wr_traverse.h
-  const size_t nn = s.nodes.size(), nr = s.refs.size(), np = s.prims.size();
-  std::vector<uint2> nodes(nn);
-  for (size_t i = 0; i < nn; ++i) {
-    const wr::KdNode& k = s.nodes[i];
-    if (k.axis >= 0) {
-      uint32_t bits;
-      std::memcpy(&bits, &k.split, 4);
-      nodes[i] = make_uint2(bits, (static_cast<uint32_t>(k.right) << 2) | static_cast<uint32_t>(k.axis));
-    } else {
-      nodes[i] = make_uint2(static_cast<uint32_t>(k.first), (static_cast<uint32_t>(k.count) << 2) | 3u);
-    }
-  }
-  std::vector<uint4> nrec(nn);
-  std::vector<uint2> nrec_r(nn, make_uint2(0u, 0u));
-  for (size_t i = 0; i < nn; ++i) {
-    const uint2 self = nodes[i];
-    uint2 l = make_uint2(0u, 0u);
-    if (s.nodes[i].axis >= 0) {
-      l = nodes[i + 1];
-      nrec_r[i] = nodes[static_cast<size_t>(s.nodes[i].right)];
-    }
-    nrec[i] = make_uint4(self.x, self.y, l.x, l.y);
-  }
-  // multi-level records (WR_NODE_LEVELS = 3 or 4): node i's subtree of
-  // kRecLevels levels in heap order (entry 0 = i, entries 2h+1 / 2h+2 = the
-  // children of entry h; 0 below a leaf), two entries per uint4
-  std::vector<uint4> nrec3(kRecU4 * nn, make_uint4(0u, 0u, 0u, 0u));
-  {
-    constexpr int kEnt = (1 << kRecLevels) - 1;
-    for (size_t i = 0; i < nn; ++i) {
-      int64_t e[kEnt];
-      e[0] = static_cast<int64_t>(i);
-      for (int h = 0; 2 * h + 2 < kEnt; ++h) {
-        e[2 * h + 1] = e[2 * h + 2] = -1;
-        if (e[h] >= 0 && s.nodes[static_cast<size_t>(e[h])].axis >= 0) {
-          e[2 * h + 1] = e[h] + 1;
-          e[2 * h + 2] = s.nodes[static_cast<size_t>(e[h])].right;
-        }
-      }
-      uint32_t* w = reinterpret_cast<uint32_t*>(&nrec3[kRecU4 * i]);
-      for (int h = 0; h < kEnt; ++h) {
-        const uint2 v = e[h] >= 0 ? nodes[static_cast<size_t>(e[h])] : make_uint2(0u, 0u);
-        w[2 * h] = v.x;
-        w[2 * h + 1] = v.y;
-      }
-    }
-  }
-  std::vector<float4> ra(nr), rb(nr);
-  std::vector<float2> rcv(nr);
-  for (size_t i = 0; i < nr; ++i) {
-    const int pi = s.refs[i];
-    const wr::Prim& p = s.prims[pi];
-    if (p.type == wr::kTri) {
-      // A..F exactly as Triangle::hit forms them (triangle.cpp:24-30)
-      ra[i] = make_float4(p.p0.x, p.p0.y, p.p0.z, p.p0.x - p.p1.x);
-      rb[i] = make_float4(p.p0.y - p.p1.y, p.p0.z - p.p1.z, p.p0.x - p.p2.x, p.p0.y - p.p2.y);
-      float pb;
-      std::memcpy(&pb, &pi, 4);
-      rcv[i] = make_float2(p.p0.z - p.p2.z, pb);
-    } else {
-      ra[i] = make_float4(0, 0, 0, 0);
-      rb[i] = make_float4(0, 0, 0, 0);
-      int neg = -(pi + 1);
-      float pb;
-      std::memcpy(&pb, &neg, 4);
-      rcv[i] = make_float2(0.f, pb);
-    }
-  }
-  std::vector<int> pmat(np), ptype(np);
-  std::vector<float4> ptri(np), psph(np), psb0(np);
-  std::vector<float2> ptri2(np), psb1(np);
-  for (size_t i = 0; i < np; ++i) {
-    const wr::Prim& p = s.prims[i];
-    pmat[i] = p.mat;
-    ptype[i] = p.type;
-    ptri[i] = make_float4(p.p0.x - p.p1.x, p.p0.y - p.p1.y, p.p0.z - p.p1.z, p.p0.x - p.p2.x);
-    ptri2[i] = make_float2(p.p0.y - p.p2.y, p.p0.z - p.p2.z);
-    psph[i] = make_float4(p.c.x, p.c.y, p.c.z, p.r);
-    psb0[i] = make_float4(p.bl.x, p.bl.y, p.bl.z, p.br.x);
-    psb1[i] = make_float2(p.br.y, p.br.z);
-  }
-  std::vector<DLight> lights(s.lights.size());
-  for (size_t i = 0; i < lights.size(); ++i) {
-    const wr::Light& l = s.lights[i];
-    auto V = [](wr::F3 f) { return v3(f.x, f.y, f.z); };
-    lights[i] = DLight{V(l.p0), V(l.d1), V(l.d2), V(l.fx), V(l.fy), V(l.fz), V(l.le), l.inv_area};
-  }
-  std::vector<DMat> mats(std::max<size_t>(1, s.mats.size()));
-  for (size_t i = 0; i < s.mats.size(); ++i) {
-    const wr::Material& m = s.mats[i];
-    mats[i] = DMat{v3(m.diffuse.x, m.diffuse.y, m.diffuse.z), v3(m.phong.x, m.phong.y, m.phong.z),
-                   v3(m.specular.x, m.specular.y, m.specular.z), m.phong_exp, m.index};
-  }
-  auto total = measure([&](Arena& a) {
-    a.take<uint4>(nn); a.take<uint2>(nn); a.take<uint4>(kRecU4 * nn); a.take<float4>(nr); a.take<float4>(nr);
-    a.take<float2>(nr);
-    a.take<int>(np); a.take<int>(np); a.take<float4>(np); a.take<float2>(np); a.take<float4>(np);
-    a.take<float4>(np); a.take<float2>(np); a.take<float4>(2 * np); a.take<DLight>(lights.size() + 1);
-    a.take<DMat>(mats.size());
-    a.take<DevCounters>(1);
-  });
-  if (int rc = c->scene_mem.reserve(total)) {
-    delete c;
-    return rc;
-  }
-  Arena& A = c->scene_mem;
-  auto up = [&](auto* dst, const auto& v) {
-    return hipMemcpy(dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
-  };
-  DevScene& d = c->ds;
-  uint4* dn = A.take<uint4>(nn);
-  uint2* dnr = A.take<uint2>(nn);
-  uint4* dn3 = A.take<uint4>(kRecU4 * nn);
-  float4* dra = A.take<float4>(nr);
-  float4* drb = A.take<float4>(nr);
-  float2* drc = A.take<float2>(nr);
-  int* dpm = A.take<int>(np);
-  int* dpt = A.take<int>(np);
-  float4* dptri = A.take<float4>(np);
-  float2* dptri2 = A.take<float2>(np);
-  float4* dpsph = A.take<float4>(np);
-  float4* dpsb0 = A.take<float4>(np);
-  float2* dpsb1 = A.take<float2>(np);
-  float4* dprec = A.take<float4>(2 * np);
-  std::vector<float4> prec(2 * np);
-  for (size_t i = 0; i < np; ++i) {
-    prec[2 * i] = ptri[i];
-    float mb, tb;  // the int fields' bits (host code: no __int_as_float)
-    std::memcpy(&mb, &pmat[i], 4);
-    std::memcpy(&tb, &ptype[i], 4);
-    prec[2 * i + 1] = make_float4(ptri2[i].x, ptri2[i].y, mb, tb);
-  }
-  DLight* dl = A.take<DLight>(lights.size() + 1);
-  DMat* dm = A.take<DMat>(mats.size());
-  c->ctr = A.take<DevCounters>(1);
-  hipError_t e = hipSuccess;
-  for (hipError_t x : {up(dn, nrec), up(dnr, nrec_r), up(dn3, nrec3), up(dra, ra), up(drb, rb), up(drc, rcv), up(dpm, pmat), up(dpt, ptype),
-                       up(dptri, ptri), up(dptri2, ptri2), up(dpsph, psph), up(dpsb0, psb0), up(dpsb1, psb1), up(dprec, prec),
-                       up(dm, mats)})
-    if (x != hipSuccess) e = x;
-  if (!lights.empty() && e == hipSuccess) e = up(dl, lights);
-  if (e != hipSuccess) {
-    wr_destroy(c);
-    return fail(WR_E_HIP, std::string("scene upload: ") + hipGetErrorString(e));
-  }
-  d.nrec = dn;
-  d.nrec_r = dnr;
-  d.nrec3 = dn3;
-  d.ref_a = dra;
-  d.ref_b = drb;
-  d.ref_c = drc;
-  d.prim_mat = dpm;
-  d.prim_type = dpt;
-  d.prim_tri = dptri;
-  d.prim_tri2 = dptri2;
-  d.prim_sph = dpsph;
-  d.prim_rec = dprec;
-  d.prim_sbox0 = dpsb0;
-  d.prim_sbox1 = dpsb1;
+// The knobs that act on what the scene's trees turn out to be: read here,
+// applied by the steps that build them.  -1: not set.
+struct SceneKnobs {
+  int trace_wide = -1;         // test knob: 1 runs the 32-bit-stack KD walk on any tree
+  int trace_waves_per_cu = -1;  // diagnostic: caps the KD walk's resident waves
+  int bvh_wide = -1;           // 2 | 4 (| 8 in a WR_BVH_WIDE=8 build) forces the search tree's width
+  int walk_wave = -1;          // 0: no kd_walk_wave
+  int pair_record = -1;        // near-ties: 2 the pair list, 1 the record in the tie list only, 0 neither
+  int fast_waves_per_cu = -1;  // diagnostic: caps the search's resident waves
+  int trace_bvh = -1;          // 0: contexts start in the reference KD walk
+  int bvh_diag = 0;
+  int bvh_verify = -1;
+};
+static SceneKnobs read_scene_knobs() {
+  SceneKnobs k;
+  if (const char* e = std::getenv("WR_TRACE_WIDE")) k.trace_wide = std::atoi(e) != 0;
+  if (const char* e = std::getenv("WR_TRACE_WAVES_PER_CU")) k.trace_waves_per_cu = std::max(1, std::atoi(e));
+  if (const char* e = std::getenv("WR_BVH_WIDE")) k.bvh_wide = std::atoi(e);
+  if (const char* e = std::getenv("WR_WALK_WAVE")) k.walk_wave = std::atoi(e) != 0;
+  if (const char* e = std::getenv("WR_PAIR_RECORD")) k.pair_record = std::max(0, std::min(2, std::atoi(e)));
+  if (const char* e = std::getenv("WR_FAST_WAVES_PER_CU")) k.fast_waves_per_cu = std::max(1, std::atoi(e));
+  if (const char* e = std::getenv("WR_TRACE_BVH")) k.trace_bvh = std::atoi(e) != 0;
+  if (const char* e = std::getenv("WR_BVH_DIAG")) k.bvh_diag = std::atoi(e);
+  if (const char* e = std::getenv("WR_BVH_VERIFY")) k.bvh_verify = std::atoi(e) != 0;
+  return k;
+}
+
+// the flattened scene (wr_flatten.h) into the scene arena, and what the
+// context keeps of it
+static int upload_scene(wr_context& c, const wr::Scene& s, const wr::SceneFlat& f, const SceneKnobs& k) {
+  DevScene& d = c.ds;
+  Upload up;
+  up.add(&d.nrec, f.nrec);
+  up.add(&d.nrec_r, f.nrec_r);
+  up.add(&d.nrec3, f.nrec3);
+  up.add(&d.ref_a, f.ref_a);
+  up.add(&d.ref_b, f.ref_b);
+  up.add(&d.ref_c, f.ref_c);
+  up.add(&d.prim_mat, f.prim_mat);
+  up.add(&d.prim_type, f.prim_type);
+  up.add(&d.prim_tri, f.prim_tri);
+  up.add(&d.prim_tri2, f.prim_tri2);
+  up.add(&d.prim_sph, f.prim_sph);
+  up.add(&d.prim_sbox0, f.prim_sbox0);
+  up.add(&d.prim_sbox1, f.prim_sbox1);
+  up.add(&d.prim_rec, f.prim_rec);
+  up.add(&d.lights, f.lights, f.lights.size() + 1);
+  up.add(&d.mats, f.mats);
+  up.room(&c.ctr, 1);
+  if (int rc = up.commit(c.scene_mem, "scene")) return rc;
+  d.nlights = static_cast<int>(f.lights.size());
   d.root_l = v3(s.root_l.x, s.root_l.y, s.root_l.z);
   d.root_r = v3(s.root_r.x, s.root_r.y, s.root_r.z);
-  d.max_stack = std::max(1, s.max_stack);
-  c->sph_r = s.sph_r;
-  c->nmats = static_cast<int>(mats.size());
-  c->has_sph = std::any_of(ptype.begin(), ptype.end(), [](int t) { return t != 0; }) ? 1 : 0;
-  d.nlights = static_cast<int>(s.lights.size());
-  d.lights = dl;
-  d.mats = dm;
+  d.max_stack = f.max_stack;
   d.cam.pos = v3(s.cam.pos.x, s.cam.pos.y, s.cam.pos.z);
   d.cam.fwd = v3(s.cam.fwd.x, s.cam.fwd.y, s.cam.fwd.z);
   d.cam.xres = s.cam.xres;
@@ -1990,184 +1975,133 @@ int wr_create(const wr_scene* sc, int device, wr_context** out) {
   d.cam.plane_dist = s.cam.plane_dist;
   std::memcpy(d.cam.w2r, s.cam.w2r, sizeof d.cam.w2r);
   std::memcpy(d.cam.r2w, s.cam.r2w, sizeof d.cam.r2w);
-  c->scene_bytes = static_cast<int64_t>(A.used);
-  for (const auto& p : s.prims) c->spheres |= p.type != wr::kTri;
-  if (const char* e = std::getenv("WR_TRACE_STAMPS")) c->stamps = std::atoi(e) != 0 && !c->spheres;
-  if (const char* e = std::getenv("WR_TRACE_LOG")) c->trace_log = std::atoi(e) != 0;
-  if (const char* e = std::getenv("WR_TRACE_DENSE")) c->api_dense = std::atoi(e) != 0;
-  if (const char* e = std::getenv("WR_TRACE_NO_CUT")) c->no_cut = std::atoi(e) != 0;
-  if (const char* e = std::getenv("WR_VCM_CELL")) c->vcm_cell = std::min(8.f, std::max(0.25f, (float)std::atof(e)));
-  {
-    // persistent traversal grid: the one-wave workgroups that fit at once (LDS stack
-    // and registers); more would only queue behind the first wave of blocks
-    // 16-bit stack nodes and 16-bit pair offsets (64 lanes x kLeavesPerRound
-    // leaves x max leaf size < 65536)
-    int max_leaf = 0;
-    for (const auto& k : s.nodes)
-      if (k.axis < 0) max_leaf = std::max(max_leaf, k.count);
-    c->narrow = nn <= 65536 && static_cast<int64_t>(max_leaf) * 64 * kLeavesPerRound < 65536;
-    // test knob: WR_TRACE_WIDE=1 runs the 32-bit-stack variant on any tree
-    if (const char* e = std::getenv("WR_TRACE_WIDE")) c->narrow = c->narrow && std::atoi(e) == 0;
-    auto resident = [&](int mode) {
-      const size_t lds = trace_lds_bytes(d.max_stack, c->narrow, mode == TRACE_DENSE);
-      int per_cu = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_kernel(false, c->spheres, c->narrow, false, mode),
-                                                       kTraceBlock, lds) != hipSuccess ||
-          per_cu <= 0)
-        per_cu = 8;
-      // diagnostic: WR_TRACE_WAVES_PER_CU caps the resident traversal waves
-      // (leaving room for the other pipelines' shading kernels)
-      if (const char* e = std::getenv("WR_TRACE_WAVES_PER_CU")) per_cu = std::max(1, std::min(per_cu, std::atoi(e)));
-      return per_cu;
-    };
-    c->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    c->resolve_blocks *= c->cus;  // WR_RESOLVE_GRID was blocks per CU
-    c->trace_blocks = c->cus * resident(TRACE_PLAIN);
-    c->trace_blocks_dense = c->cus * resident(TRACE_DENSE);
+  c.scene_bytes = static_cast<int64_t>(c.scene_mem.used);
+  c.sph_r = s.sph_r;
+  c.nmats = static_cast<int>(f.mats.size());
+  c.spheres = f.spheres;
+  c.has_sph = f.spheres ? 1 : 0;
+  c.stamps = c.stamps && !c.spheres;
+  c.narrow = f.narrow && k.trace_wide <= 0;
+  return WR_OK;
+}
+
+// persistent traversal grid: the one-wave workgroups that fit at once (LDS stack
+// and registers); more would only queue behind the first wave of blocks
+static void size_kd_grids(wr_context& c, const SceneKnobs& k) {
+  auto resident = [&](int mode) {
+    const size_t lds = trace_lds_bytes(c.ds.max_stack, c.narrow, mode == TRACE_DENSE);
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_kernel(false, c.spheres, c.narrow, false, mode),
+                                                     kTraceBlock, lds) != hipSuccess ||
+        per_cu <= 0)
+      per_cu = 8;
+    // (leaving room for the other pipelines' shading kernels)
+    if (k.trace_waves_per_cu > 0) per_cu = std::min(per_cu, k.trace_waves_per_cu);
+    return per_cu;
+  };
+  c.trace_blocks = c.cus * resident(TRACE_PLAIN);
+  c.trace_blocks_dense = c.cus * resident(TRACE_DENSE);
+}
+
+// the search tree's width: 4-wide for scenes whose binary tree outgrows
+// the L2 (its nodes then come from the Infinity Cache / HBM, and one
+// 128-byte node holds two of the binary tree's levels: C4 +5-8 %, while
+// L2-resident scenes lose 1-4 %: DESIGN.md 4b); WR_BVH_WIDE=2|4 forces
+static int bvh_width(const wr::Scene& s, const SceneKnobs& k) {
+  size_t tris = 0;
+  for (const wr::Prim& p : s.prims) tris += p.type == wr::kTri ? 1 : 0;
+  int wide = WR_BVH_WIDE;
+  if (wide == 2 && tris >= wrf::kWide4MinTris) wide = 4;
+  if (k.bvh_wide == 2 || k.bvh_wide == 4 || (k.bvh_wide == 8 && WR_BVH_WIDE == 8)) wide = k.bvh_wide;
+  // the 8-wide search is instantiated for triangle leaves only: a scene with
+  // spheres searches the 4-wide tree, whose kernels run the sphere test
+  if (wide == 8 && tris != s.prims.size()) wide = 4;
+  return wide;
+}
+
+// ---- verified-BVH traversal data (wr_bvh.h): BVH nodes, triangle records
+// in leaf order, and the KD root paths of every primitive's leaves; then the
+// search's grid.  A scene build_fast declines keeps the KD walk (fast_ok false).
+static int upload_bvh(wr_context& c, const wr::Scene& s, const wr::SceneFlat& f, const SceneKnobs& k) {
+  const int wide = bvh_width(s, k);
+  wrf::FastHost fh;
+  wrf::build_fast(s, fh, wide, wide == 2);
+  if (!fh.ok) return WR_OK;
+  FastScene& fs = c.fs;
+  Upload up;
+  up.add(&fs.nodes, fh.nodes);
+  up.add(&fs.tris, fh.tris);
+  up.add(&fs.prim_leaf_off, fh.prim_leaf_off);
+  up.add(&fs.prim_leaf, fh.prim_leaf, 1);
+  up.add(&fs.prim_leaf_pos, fh.prim_leaf_pos, std::max<size_t>(1, fh.prim_leaf.size()));
+  up.add(&fs.path, fh.path);
+  up.add(&fs.node_path, fh.node_path);
+  up.add(&fs.node_cell, fh.node_cell);
+  up.add(&fs.prim_rec, fh.prim_rec);
+  up.add(&fs.nodes4, fh.nodes4);
+  up.add(&fs.nodes8, fh.nodes8);
+  if (int rc = up.commit(c.fast_mem, "BVH")) return rc;
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = std::min(fh.nodes[0].b[a], fh.nodes[0].b[6 + a]);
+    hi[a] = std::max(fh.nodes[0].b[3 + a], fh.nodes[0].b[9 + a]);
   }
-  // ---- verified-BVH traversal data (wr_bvh.h): BVH nodes, triangle records
-  // in leaf order, and the KD root paths of every primitive's leaves
-  {
-    // the search tree's width: 4-wide for scenes whose binary tree outgrows
-    // the L2 (its nodes then come from the Infinity Cache / HBM, and one
-    // 128-byte node holds two of the binary tree's levels: C4 +5-8 %, while
-    // L2-resident scenes lose 1-4 %: DESIGN.md 4b); WR_BVH_WIDE=2|4 forces
-    int wide = WR_BVH_WIDE;
-    if (wide == 2) {
-      size_t tris = 0;
-      for (const wr::Prim& p : s.prims) tris += p.type == wr::kTri ? 1 : 0;
-      if (tris >= wrf::kWide4MinTris) wide = 4;
-    }
-    if (const char* e = std::getenv("WR_BVH_WIDE")) {
-      const int w = std::atoi(e);
-      if (w == 2 || w == 4 || (w == 8 && WR_BVH_WIDE == 8)) wide = w;
-    }
-    // the 8-wide search is instantiated for triangle leaves only: a scene with
-    // spheres searches the 4-wide tree, whose kernels run the sphere test
-    if (wide == 8)
-      for (const wr::Prim& p : s.prims)
-        if (p.type != wr::kTri) {
-          wide = 4;
-          break;
-        }
-    wrf::FastHost fh;
-    wrf::build_fast(s, fh, wide, wide == 2);
-    if (fh.ok) {
-      const size_t fbn = fh.nodes.size(), ftr = fh.tris.size(), fpo = fh.prim_leaf_off.size(),
-                   fpl = std::max<size_t>(1, fh.prim_leaf.size()), fpa = fh.path.size() / 2;
-      const size_t fnp = fh.node_path.size();
-      const size_t fbytes = measure([&](Arena& a) {
-        a.take<wrf::BNode>(fbn); a.take<wrf::TriRec>(ftr); a.take<int>(fpo); a.take<int>(fpl); a.take<int>(fpl);
-        a.take<uint2>(fpa); a.take<int>(fnp); a.take<float4>(2 * fnp); a.take<wrf::PrimRec>(fh.prim_rec.size());
-        a.take<wrf::BNode4S>(fh.nodes4.size());
-        a.take<wrf::BNode8>(fh.nodes8.size());
-      });
-      if (int rc = c->fast_mem.reserve(fbytes)) {
-        wr_destroy(c);
-        return rc;
-      }
-      Arena& F = c->fast_mem;
-      auto* dno = F.take<wrf::BNode>(fbn);
-      auto* dtr = F.take<wrf::TriRec>(ftr);
-      int* dpo = F.take<int>(fpo);
-      int* dpl = F.take<int>(fpl);
-      int* dpp = F.take<int>(fpl);
-      uint2* dpa = F.take<uint2>(fpa);
-      int* dnp = F.take<int>(fnp);
-      float4* dnc = F.take<float4>(2 * fnp);
-      auto* dpr = F.take<wrf::PrimRec>(fh.prim_rec.size());
-      auto* dn4 = F.take<wrf::BNode4S>(fh.nodes4.size());
-      auto* dn8 = F.take<wrf::BNode8>(fh.nodes8.size());
-      hipError_t fe = hipSuccess;
-      for (hipError_t x : {hipMemcpy(dno, fh.nodes.data(), fbn * sizeof(wrf::BNode), hipMemcpyHostToDevice),
-                           hipMemcpy(dtr, fh.tris.data(), ftr * sizeof(wrf::TriRec), hipMemcpyHostToDevice),
-                           hipMemcpy(dpo, fh.prim_leaf_off.data(), fpo * sizeof(int), hipMemcpyHostToDevice),
-                           hipMemcpy(dpl, fh.prim_leaf.data(), fh.prim_leaf.size() * sizeof(int), hipMemcpyHostToDevice),
-                           hipMemcpy(dpp, fh.prim_leaf_pos.data(), fh.prim_leaf_pos.size() * sizeof(int),
-                                     hipMemcpyHostToDevice),
-                           hipMemcpy(dpa, fh.path.data(), fpa * sizeof(uint2), hipMemcpyHostToDevice),
-                           hipMemcpy(dnp, fh.node_path.data(), fnp * sizeof(int), hipMemcpyHostToDevice),
-                           hipMemcpy(dnc, fh.node_cell.data(), 8 * fnp * sizeof(float), hipMemcpyHostToDevice),
-                           hipMemcpy(dpr, fh.prim_rec.data(), fh.prim_rec.size() * sizeof(wrf::PrimRec),
-                                     hipMemcpyHostToDevice),
-                           hipMemcpy(dn4, fh.nodes4.data(), fh.nodes4.size() * sizeof(wrf::BNode4S),
-                                     hipMemcpyHostToDevice),
-                           hipMemcpy(dn8, fh.nodes8.data(), fh.nodes8.size() * sizeof(wrf::BNode8),
-                                     hipMemcpyHostToDevice)})
-        if (x != hipSuccess) fe = x;
-      if (fe != hipSuccess) {
-        wr_destroy(c);
-        return fail(WR_E_HIP, std::string("BVH upload: ") + hipGetErrorString(fe));
-      }
-      FastScene& fs = c->fs;
-      fs.nodes = reinterpret_cast<const float4*>(dno);
-      fs.tris = reinterpret_cast<const float4*>(dtr);
-      fs.prim_leaf_off = dpo;
-      fs.prim_leaf = dpl;
-      fs.prim_leaf_pos = dpp;
-      fs.path = dpa;
-      fs.node_path = dnp;
-      fs.node_cell = dnc;
-      fs.prim_rec = reinterpret_cast<const float4*>(dpr);
-      fs.nodes4 = reinterpret_cast<const float4*>(dn4);
-      fs.nodes8 = reinterpret_cast<const float4*>(dn8);
-      float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-      for (int k = 0; k < 3; ++k) {
-        lo[k] = std::min(fh.nodes[0].b[k], fh.nodes[0].b[6 + k]);
-        hi[k] = std::max(fh.nodes[0].b[3 + k], fh.nodes[0].b[9 + k]);
-      }
-      fs.lo = v3(lo[0], lo[1], lo[2]);
-      fs.hi = v3(hi[0], hi[1], hi[2]);
-      fs.sph = fh.spheres > 0 ? 1 : 0;
-      fs.org_lo = v3(fh.org_lo[0], fh.org_lo[1], fh.org_lo[2]);
-      fs.org_hi = v3(fh.org_hi[0], fh.org_hi[1], fh.org_hi[2]);
-      // the search's stack holds BVH entries only; the hard rays' kernel walks
-      // both trees
-      fs.wide = wide;
-      fs.sdepth = wide == 8 ? 7 * fh.depth8 + 1 : wide == 4 ? 3 * fh.depth4 + 1 : fh.depth + 1;
-      if (wide == 2 && !fh.nodes4.empty()) {
-        c->sdepth4 = 3 * fh.depth4 + 1;
-        c->fs4_ok = true;
-      }
-      if (const char* e = std::getenv("WR_BVH_WIDE_LAT")) c->lat_wide = std::atoi(e) != 0;
-      fs.depth = std::max(fh.depth + 1, d.max_stack + 1);
-      // kd_walk_wave: node index and depth share a word, the leaf key and the
-      // position in the leaf 64 bits (the key's lowest bit is 64 - dep_max, so
-      // every leaf must hold fewer than 2^(64 - dep_max) references)
-      size_t kd_max_leaf = 0;
-      for (const auto& k : s.nodes)
-        if (k.axis < 0) kd_max_leaf = std::max(kd_max_leaf, static_cast<size_t>(k.count));
-      fs.walk_wave = s.nodes.size() < (size_t(1) << 26) && s.dep_max <= 43 &&
-                             kd_max_leaf < (size_t(1) << (64 - std::max(s.dep_max, 0)))
-                         ? 1
-                         : 0;
-      if (const char* e = std::getenv("WR_WALK_WAVE")) fs.walk_wave = fs.walk_wave && std::atoi(e) != 0;
-      // near-ties and the search's pair record (kPairWindow): 2 = the pair list
-      // (one per lane), 1 = the record in the tie list only, 0 = neither
-      fs.pair = 2;
-      if (const char* e = std::getenv("WR_PAIR_RECORD")) fs.pair = std::max(0, std::min(2, std::atoi(e)));
-      c->fast_ok = true;
-      if (const char* e = std::getenv("WR_RESOLVE_LIST")) c->resolve_list = std::atoi(e) != 0;
-      int per_cu = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fast_kernel<false, false>(wide, fs.sph, c->resolve_list), kTraceBlock,
-                                                       search_lds_bytes(fs.sdepth, wide) + (c->resolve_list ? kRlistLds : 0)) != hipSuccess ||
-          per_cu <= 0)
-        per_cu = 8;
-      // diagnostic: WR_FAST_WAVES_PER_CU caps the search's resident waves
-      if (const char* e = std::getenv("WR_FAST_WAVES_PER_CU")) per_cu = std::max(1, std::min(per_cu, std::atoi(e)));
-      c->fast_blocks = c->cus * per_cu;
-      // the verified BVH is the default traversal (same answers as the KD
-      // walk); WR_TRACE_BVH=0 selects the walk
-      c->fast_on = true;
-      if (const char* e = std::getenv("WR_TRACE_BVH")) c->fast_on = std::atoi(e) != 0;
-      if (const char* e = std::getenv("WR_BVH_DIAG")) fs.diag = std::atoi(e);
-      if (const char* e = std::getenv("WR_BVH_VERIFY")) c->verify = std::atoi(e) != 0;
-      if (c->trace_log)
-        std::fprintf(stderr, "[wr bvh] nodes %zu tris %zu depth %d lds %zu B/wave, %d waves/CU -> grid %d; kd grid %d\n",
-                     fbn, ftr, fs.sdepth, search_lds_bytes(fs.sdepth, wide), per_cu, c->fast_blocks, c->trace_blocks);
-    }
+  fs.lo = v3(lo[0], lo[1], lo[2]);
+  fs.hi = v3(hi[0], hi[1], hi[2]);
+  fs.sph = fh.spheres > 0 ? 1 : 0;
+  fs.org_lo = v3(fh.org_lo[0], fh.org_lo[1], fh.org_lo[2]);
+  fs.org_hi = v3(fh.org_hi[0], fh.org_hi[1], fh.org_hi[2]);
+  // the search's stack holds BVH entries only; the hard rays' kernel walks
+  // both trees
+  fs.wide = wide;
+  fs.sdepth = wide == 8 ? 7 * fh.depth8 + 1 : wide == 4 ? 3 * fh.depth4 + 1 : fh.depth + 1;
+  if (wide == 2 && !fh.nodes4.empty()) {
+    c.sdepth4 = 3 * fh.depth4 + 1;
+    c.fs4_ok = true;
   }
-  *out = c;
+  fs.depth = std::max(fh.depth + 1, c.ds.max_stack + 1);
+  fs.walk_wave = f.walk_wave && k.walk_wave != 0 ? 1 : 0;
+  fs.pair = k.pair_record >= 0 ? k.pair_record : 2;
+  fs.diag = k.bvh_diag;
+  c.fast_ok = true;
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fast_kernel<false, false>(wide, fs.sph, c.resolve_list), kTraceBlock,
+                                                   search_lds_bytes(fs.sdepth, wide) + (c.resolve_list ? kRlistLds : 0)) != hipSuccess ||
+      per_cu <= 0)
+    per_cu = 8;
+  if (k.fast_waves_per_cu > 0) per_cu = std::min(per_cu, k.fast_waves_per_cu);
+  c.fast_blocks = c.cus * per_cu;
+  // the verified BVH is the default traversal (same answers as the KD
+  // walk); WR_TRACE_BVH=0 selects the walk
+  c.fast_on = k.trace_bvh != 0;
+  if (k.bvh_verify >= 0) c.verify = k.bvh_verify != 0;
+  if (c.trace_log)
+    std::fprintf(stderr, "[wr bvh] nodes %zu tris %zu depth %d lds %zu B/wave, %d waves/CU -> grid %d; kd grid %d\n",
+                 fh.nodes.size(), fh.tris.size(), fs.sdepth, search_lds_bytes(fs.sdepth, wide), per_cu, c.fast_blocks,
+                 c.trace_blocks);
+  return WR_OK;
+}
+
+int wr_create(const wr_scene* sc, int device, wr_context** out) {
+  if (!sc || !out) return fail(WR_E_ARG, "null argument");
+  *out = nullptr;
+  latch_hw_queues();  // before the library's first HIP call: the value HIP reads
+  if (int rc = check_device()) return rc;
+  DeviceGuard dg;
+  const wr::Scene& s = sc->s;
+  if (int rc = check_scene(s)) return rc;
+  HIPCHK(hipSetDevice(device));
+  ContextPtr c(new wr_context());
+  c->device = device;
+  if (int rc = make_streams(*c)) return rc;
+  read_knobs(*c);
+  const SceneKnobs k = read_scene_knobs();
+  wr::SceneFlat flat;
+  wr::flatten_scene(s, flat);
+  if (int rc = upload_scene(*c, s, flat, k)) return rc;
+  size_kd_grids(*c, k);
+  if (int rc = upload_bvh(*c, s, flat, k)) return rc;
+  *out = c.release();
   return WR_OK;
 }
 
@@ -2195,52 +2129,16 @@ void wr_destroy(wr_context* c) {
   c->dev_comms.clear();
   if (c->comm) (void)rccl().destroy(c->comm);
   c->comm = nullptr;
-  (void)hipSetDevice(c->device);
+  (void)hipSetDevice(c->device);  // the members' destructors free on it
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (Pipe& p : c->pipes) {
+  for (Pipe& p : c->pipes)
     if (p.stream) (void)hipStreamSynchronize(p.stream);
-    for (hipEvent_t e : p.events) (void)hipEventDestroy(e);
-    if (p.done) (void)hipEventDestroy(p.done);
-    p.late_mem.release();
-    if (p.ctr) (void)hipFree(p.ctr);
-    if (p.sc) (void)hipFree(p.sc);
-    p.work.release();
-    for (float* f : p.mom)
-      if (f) (void)hipFree(f);
-    if (p.stream && p.stream != c->stream) (void)hipStreamDestroy(p.stream);
-  }
-  if (c->t_ref) (void)hipEventDestroy(c->t_ref);
-  if (c->t_null) (void)hipEventDestroy(c->t_null);
-  if (c->film_tmp) (void)hipFree(c->film_tmp);
-  if (c->film_bak) (void)hipFree(c->film_bak);
-  if (c->err_acc) (void)hipFree(c->err_acc);
-  if (c->host_ctr) (void)hipHostFree(c->host_ctr);
-  if (c->api_tmp) (void)hipFree(c->api_tmp);
-  if (c->api_t2) (void)hipFree(c->api_t2);
-  if (c->api_spill) (void)hipFree(c->api_spill);
-  for (Pipe& p : c->pipes) {
-    if (p.t2buf) (void)hipFree(p.t2buf);
-    if (p.spill) (void)hipFree(p.spill);
-  }
-  if (c->red_buf) (void)hipFree(c->red_buf);
-  if (c->stage_buf) (void)hipFree(c->stage_buf);
-  c->fast_mem.release();
-  c->scene_mem.release();
-  if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
 
 // the context's API scratch block, at least `bytes` (the stream is idle
 // between API calls: every call ends with a stream synchronize)
-static int api_scratch(wr_context* c, size_t bytes) {
-  if (c->api_tmp_n >= bytes) return WR_OK;
-  if (c->api_tmp) (void)hipFree(c->api_tmp);
-  c->api_tmp = nullptr;
-  c->api_tmp_n = 0;
-  HIPCHK(hipMalloc(&c->api_tmp, bytes));
-  c->api_tmp_n = bytes;
-  return WR_OK;
-}
+static int api_scratch(wr_context* c, size_t bytes) { return c->api_tmp.grow(bytes); }
 
 static int trace_api(wr_context* c, const wr_ray* rays, const float* targets, int64_t n64, wr_hit* hits,
                      uint8_t* occ) {
@@ -2254,7 +2152,7 @@ static int trace_api(wr_context* c, const wr_ray* rays, const float* targets, in
   const size_t nb = size_t(n);
   const size_t bytes = nb * (sizeof(wr_ray) + 4 * 14 + sizeof(wr_hit) + 1) + 16 * 256;
   if (int rc = api_scratch(c, bytes)) return rc;
-  char* q = c->api_tmp;
+  char* q = c->api_tmp.p;
   auto take = [&](size_t sz) { char* r = q; q += (sz + 255) & ~size_t(255); return r; };
   wr_ray* dr = reinterpret_cast<wr_ray*>(take(nb * sizeof(wr_ray)));
   float* o3 = reinterpret_cast<float*>(take(nb * 12));
@@ -2276,18 +2174,13 @@ static int trace_api(wr_context* c, const wr_ray* rays, const float* targets, in
   c->timing = false;
   Timer tm(c, nullptr);
   HIPCHK(hipMemsetAsync(c->ctr, 0, sizeof(DevCounters), c->stream));
-  if (c->fast_on && c->api_t2_cap < nb) {
-    if (c->api_t2) (void)hipFree(c->api_t2);
-    c->api_t2 = nullptr;
-    c->api_t2_cap = 0;
-    HIPCHK(hipMalloc(&c->api_t2, 5 * nb * sizeof(float)));  // as ensure_t2
-    c->api_t2_cap = nb;
-  }
+  if (c->fast_on)
+    if (int rc = c->api_t2.grow(5 * nb)) return rc;  // as ensure_t2
   QueueList ql;
   ql.add(rq(o3, d3, n, cnt, tt, pr, tmn, tmx, occ ? dcut : nullptr), n);
-  if (c->fast_on && !c->api_spill && max_spill_entries(c) > 0)
-    HIPCHK(hipMalloc(&c->api_spill, max_spill_entries(c) * size_t(c->fast_blocks) * 64 * sizeof(int2)));
-  const TraceSlot ts{&c->ctr->fetch, c->api_t2, c->api_t2_cap, &c->ctr->hard[0], c->api_spill, &c->ctr->rlist};
+  if (c->fast_on && !c->api_spill.p && max_spill_entries(c) > 0)
+    if (int rc = c->api_spill.grow(max_spill_entries(c) * size_t(c->fast_blocks) * 64)) return rc;
+  const TraceSlot ts{&c->ctr->fetch, c->api_t2.p, c->api_t2.n / 5, &c->ctr->hard[0], c->api_spill.p, &c->ctr->rlist};
   trace_launch(c, c->stream, c->ctr, ts, tm, false, ql.Q, ql.max_rays,
                c->api_dense ? TRACE_DENSE : (occ != nullptr ? TRACE_CUT : TRACE_PLAIN), true);
   hipLaunchKernelGGL(k_api_finish, dim3(g), dim3(256), 0, c->stream, c->ds, o3, d3, tt, pr, dtg, n, dh,
@@ -2355,22 +2248,16 @@ static int film_target(wr_context* c, float* film, int film_on_device, size_t nf
     *dev = film;
     return WR_OK;
   }
-  if (c->film_tmp_n < nfloat) {
-    if (c->film_tmp) (void)hipFree(c->film_tmp);
-    c->film_tmp = nullptr;
-    c->film_tmp_n = 0;
-    HIPCHK(hipMalloc(&c->film_tmp, nfloat * sizeof(float)));
-    c->film_tmp_n = nfloat;
-  }
-  HIPCHK(hipMemsetAsync(c->film_tmp, 0, nfloat * sizeof(float), c->stream));
-  *dev = c->film_tmp;
+  if (int rc = c->film_tmp.grow(nfloat)) return rc;
+  HIPCHK(hipMemsetAsync(c->film_tmp.p, 0, nfloat * sizeof(float), c->stream));
+  *dev = c->film_tmp.p;
   return WR_OK;
 }
 
 static int film_return(wr_context* c, float* film, int film_on_device, size_t nfloat) {
   if (film_on_device) return WR_OK;
   std::vector<float> tmp(nfloat);
-  HIPCHK(hipMemcpyAsync(tmp.data(), c->film_tmp, nfloat * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(tmp.data(), c->film_tmp.p, nfloat * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   for (size_t i = 0; i < nfloat; ++i) film[i] = film[i] + tmp[i];
   return WR_OK;
@@ -2393,7 +2280,7 @@ static int moments_return(wr_context* c, float* film, const MomentFilms& M, int 
   if (!M.on()) return film_return(c, film, films_on_device, nf);
   if (films_on_device) return WR_OK;
   std::vector<float> tmp(2 * nf);
-  HIPCHK(hipMemcpyAsync(tmp.data(), c->film_tmp, 2 * nf * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(tmp.data(), c->film_tmp.p, 2 * nf * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   for (size_t i = 0; i < nf; ++i) film[i] = film[i] + tmp[i];
   for (size_t i = 0; i < nf; ++i) M.sq[i] = M.sq[i] + tmp[nf + i];
@@ -2407,19 +2294,14 @@ static int ensure_moments(wr_context* c, int np, size_t nf) {
   if (dirty) HIPCHK(hipDeviceSynchronize());
   for (int i = 0; i < kMaxPipes; ++i) {
     Pipe& p = c->pipes[i];
-    const bool grow = i < np && p.mom_n < nf;
-    if (!grow && !(dirty && p.mom_n)) continue;
-    const size_t had = p.mom_n;
-    if (grow) p.mom_n = 0;
-    for (int m = 0; m < kGroup; ++m) {
-      if (grow) {
-        if (p.mom[m]) (void)hipFree(p.mom[m]);
-        p.mom[m] = nullptr;
-        HIPCHK(hipMalloc(&p.mom[m], nf * sizeof(float)));
-      }
-      HIPCHK(hipMemsetAsync(p.mom[m], 0, (grow ? nf : had) * sizeof(float), c->stream));
+    const size_t had = p.mom[kGroup - 1].n;  // grown in order: the last one is the smallest
+    const bool grow = i < np && had < nf;
+    if (!grow && !(dirty && had)) continue;
+    for (DevBuf<float>& f : p.mom) {
+      if (grow)
+        if (int rc = f.grow(nf)) return rc;
+      HIPCHK(hipMemsetAsync(f.p, 0, f.n * sizeof(float), c->stream));
     }
-    if (grow) p.mom_n = nf;
   }
   c->mom_dirty = false;
   return WR_OK;
@@ -2429,7 +2311,7 @@ static int ensure_moments(wr_context* c, int np, size_t nf) {
 static void fold_launch(wr_context* c, Pipe& pp, int m, float* dfilm, float* dsq, size_t nf) {
   const size_t rounds = (nf + 4 * kFoldBlock - 1) / (4 * kFoldBlock);
   const int g = static_cast<int>(std::max<size_t>(1, std::min<size_t>(rounds, size_t(c->cus) * 8)));
-  hipLaunchKernelGGL(k_film_fold, dim3(g), dim3(kFoldBlock), 0, pp.stream, dfilm, dsq, pp.mom[m], nf);
+  hipLaunchKernelGGL(k_film_fold, dim3(g), dim3(kFoldBlock), 0, pp.stream, dfilm, dsq, pp.mom[m].p, nf);
   Timer(c, &pp).mark(WR_K_OTHER);
 }
 
@@ -2578,18 +2460,12 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
   // host film's device copy starts at zero
   const bool pooled = c->pipes[0].bb[0].vidx != nullptr;
   if (pooled && film_on_device) {
-    if (c->film_bak_n < nbak) {
-      if (c->film_bak) (void)hipFree(c->film_bak);
-      c->film_bak = nullptr;
-      c->film_bak_n = 0;
-      HIPCHK(hipMalloc(&c->film_bak, nbak * sizeof(float)));
-      c->film_bak_n = nbak;
-    }
+    if (int rc = c->film_bak.grow(nbak)) return rc;
     (void)hipEventRecord(c->t_null, nullptr);
     (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
-    HIPCHK(hipMemcpyAsync(c->film_bak, dfilm, nf * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->film_bak.p, dfilm, nf * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     if (M.on())
-      HIPCHK(hipMemcpyAsync(c->film_bak + nf, M.dsq, nf * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(hipMemcpyAsync(c->film_bak.p + nf, M.dsq, nf * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   }
   const wr_stats st0 = st ? *st : wr_stats{};
   BdptArgs A0;
@@ -2805,7 +2681,7 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
         // folded after the group that holds its last piece.
         const auto& groups = pl.per_pipe[pi];
         for (int m = 0; m < G.gn; ++m) {
-          G.GA.a[m].film = G.pp->mom[grp[m].iter % kGroup];
+          G.GA.a[m].film = G.pp->mom[grp[m].iter % kGroup].p;
           const Piece* next = m + 1 < G.gn ? &grp[m + 1]
                               : r + 1 < static_cast<int>(groups.size()) ? &groups[r + 1][0] : nullptr;
           if (!next || next->iter != grp[m].iter) G.fold[G.nfold++] = grp[m].iter % kGroup;
@@ -2831,8 +2707,8 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     if (M.on()) c->mom_dirty = true;  // pass films may hold unfolded work
     if (pooled && film_on_device) {
       (void)hipDeviceSynchronize();  // the pipelines' launches in flight
-      (void)hipMemcpy(dfilm, c->film_bak, nf * sizeof(float), hipMemcpyDeviceToDevice);
-      if (M.on()) (void)hipMemcpy(M.dsq, c->film_bak + nf, nf * sizeof(float), hipMemcpyDeviceToDevice);
+      (void)hipMemcpy(dfilm, c->film_bak.p, nf * sizeof(float), hipMemcpyDeviceToDevice);
+      if (M.on()) (void)hipMemcpy(M.dsq, c->film_bak.p + nf, nf * sizeof(float), hipMemcpyDeviceToDevice);
     }
     return rc;
   };
@@ -2850,9 +2726,9 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     // (a moments render folds only into the caller's two films, and a finished
     // run leaves every pass film folded and clear: both films go back alike)
     if (film_on_device) {
-      HIPCHK(hipMemcpyAsync(dfilm, c->film_bak, nf * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(hipMemcpyAsync(dfilm, c->film_bak.p, nf * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
       if (M.on())
-        HIPCHK(hipMemcpyAsync(M.dsq, c->film_bak + nf, nf * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(M.dsq, c->film_bak.p + nf, nf * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     } else {
       HIPCHK(hipMemsetAsync(dfilm, 0, nbak * sizeof(float), c->stream));
     }
@@ -2866,7 +2742,7 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     if (st) st->redone += 1;
   }
   if (st) {
-    for (int i = 0; i < np; ++i) st->work_bytes += static_cast<int64_t>(c->pipes[i].work.cap);
+    for (int i = 0; i < np; ++i) st->work_bytes += static_cast<int64_t>(c->pipes[i].work.cap());
     st->work_paths += static_cast<int64_t>(np) * kGroup * cap;
   }
   return moments_return(c, film, M, film_on_device, nf);
@@ -2948,7 +2824,7 @@ static int render_vcm_one(wr_context* c, const wr_vcm_params* prm, float* film, 
       X.a.sc = pp.sc + m;
       const int it = prm->iter_begin + it0 + m;
       X.a.iter = static_cast<uint32_t>(it);
-      if (M.on()) X.a.film = pp.mom[m];  // member m's iteration, folded below
+      if (M.on()) X.a.film = pp.mom[m].p;  // member m's iteration, folded below
       // runIteration's radius schedule and MIS factors (:50-64), host float
       float radius = base_radius;
       radius /= powf(static_cast<float>(it + 1), 0.5f * (1.f - prm->radius_alpha));
@@ -3048,7 +2924,7 @@ static int path_radiance_one(wr_context* c, const wr_ray* rays, int64_t n64, int
   float* dfilm = nullptr;
   if (int rc = film_target(c, rgb, 0, nf, &dfilm)) return rc;
   if (int rc = api_scratch(c, size_t(P) * sizeof(wr_ray))) return rc;
-  wr_ray* drays = reinterpret_cast<wr_ray*>(c->api_tmp);
+  wr_ray* drays = reinterpret_cast<wr_ray*>(c->api_tmp.p);
   HIPCHK(hipMemcpyAsync(drays, rays, size_t(P) * sizeof(wr_ray), hipMemcpyHostToDevice, pp.stream));
   begin_render(c, 1, 0);
   PtGroup GA;
@@ -3158,7 +3034,7 @@ static int render_path_one(wr_context* c, const wr_path_params* prm, float* film
       A[m].ctr = pp.ctr;
       A[m].sc = pp.sc + m;
       A[m].k = static_cast<uint32_t>(gk + m);
-      if (M.on()) A[m].film = pp.mom[m];  // member m's sample, folded below
+      if (M.on()) A[m].film = pp.mom[m].p;  // member m's sample, folded below
     }
     HIPCHK(hipMemsetAsync(pp.sc, 0, gn * sizeof(StepCounters), sm));
     hipLaunchKernelGGL(k_pt_gen, dim3(g, gn), dim3(kShadeBlock), 0, sm, GA);
@@ -3225,15 +3101,9 @@ static void add_stats(wr_stats* d, const wr_stats& s) {
   d->redone += s.redone;
 }
 
-static int ensure_dev_film(wr_context* d, float** buf, size_t* have, size_t nf) {
-  if (*have >= nf) return WR_OK;
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr;
-  *have = 0;
+static int ensure_dev_film(wr_context* d, DevBuf<float>& buf, size_t nf) {
   HIPCHK(hipSetDevice(d->device));
-  HIPCHK(hipMalloc(buf, nf * sizeof(float)));
-  *have = nf;
-  return WR_OK;
+  return buf.grow(nf);
 }
 
 // films[k] (on device k) summed into films[0]: one RCCL reduce over the
@@ -3261,9 +3131,9 @@ static int reduce_films(wr_context* c, const std::vector<wr_context*>& dev, cons
   for (int k = 1; k < n; ++k) {
     const float* src = films[k];
     if (dev[k]->device != c->device) {
-      if (int rc = ensure_dev_film(c, &c->stage_buf, &c->stage_n, nf)) return rc;
-      HIPCHK(hipMemcpyPeerAsync(c->stage_buf, c->device, films[k], dev[k]->device, nf * sizeof(float), c->stream));
-      src = c->stage_buf;
+      if (int rc = ensure_dev_film(c, c->stage_buf, nf)) return rc;
+      HIPCHK(hipMemcpyPeerAsync(c->stage_buf.p, c->device, films[k], dev[k]->device, nf * sizeof(float), c->stream));
+      src = c->stage_buf.p;
     }
     hipLaunchKernelGGL(k_film_accumulate, dim3(g), dim3(256), 0, c->stream, films[0], src, nf);
   }
@@ -3289,9 +3159,9 @@ static int multi_render(wr_context* c, size_t nf, float* film, int film_on_devic
       buf[0] = film;
       continue;
     }
-    if (int rc = ensure_dev_film(dev[k], &dev[k]->red_buf, &dev[k]->red_n, nf)) return rc;
-    HIPCHK(hipMemsetAsync(dev[k]->red_buf, 0, nf * sizeof(float), dev[k]->stream));
-    buf[k] = dev[k]->red_buf;
+    if (int rc = ensure_dev_film(dev[k], dev[k]->red_buf, nf)) return rc;
+    HIPCHK(hipMemsetAsync(dev[k]->red_buf.p, 0, nf * sizeof(float), dev[k]->stream));
+    buf[k] = dev[k]->red_buf.p;
   }
   std::vector<wr_stats> s(n);
   for (auto& x : s) std::memset(&x, 0, sizeof x);
@@ -3465,17 +3335,17 @@ int wr_film_error(wr_context* c, const float* film, const float* film_sq, int wi
   } else {
     DeviceGuard dg;
     HIPCHK(hipSetDevice(c->device));
-    if (!c->err_acc) HIPCHK(hipMalloc(&c->err_acc, sizeof acc));
+    if (int rc = c->err_acc.grow(4)) return rc;
     // after the caller's work on the legacy null stream, like a render
     (void)hipEventRecord(c->t_null, nullptr);
     (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
-    HIPCHK(hipMemsetAsync(c->err_acc, 0, sizeof acc, c->stream));
+    HIPCHK(hipMemsetAsync(c->err_acc.p, 0, sizeof acc, c->stream));
     const size_t blocks = (nf + kErrBlock - 1) / kErrBlock;
     const int g = static_cast<int>(std::max<size_t>(1, std::min<size_t>(blocks, size_t(c->cus) * 8)));
     hipLaunchKernelGGL(k_film_error, dim3(g), dim3(kErrBlock), 0, c->stream, film, film_sq, nf, n_passes, stderr_map,
-                       c->err_acc);
+                       c->err_acc.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(acc, c->err_acc, sizeof acc, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(acc, c->err_acc.p, sizeof acc, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   out->sum_stderr = acc[0];
@@ -3504,25 +3374,24 @@ int wr_create_multi(const wr_scene* sc, const int* devices, int n, wr_context** 
     if (devices[k] < 0 || devices[k] >= have)
       return fail(WR_E_ARG, "device " + std::to_string(devices[k]) + " not visible (" + std::to_string(have) + ")");
   // one context per device, created concurrently (scene upload + BVH build each)
-  std::vector<wr_context*> ctx(n, nullptr);
+  std::vector<ContextPtr> ctx(n);
   std::vector<int> rc(n, WR_OK);
   std::vector<std::string> msg(n);
   {
     std::vector<std::thread> th;
     for (int k = 0; k < n; ++k)
       th.emplace_back([&, k] {
-        rc[k] = wr_create(sc, devices[k], &ctx[k]);
+        wr_context* made = nullptr;
+        rc[k] = wr_create(sc, devices[k], &made);
+        ctx[k].reset(made);
         if (rc[k] != WR_OK) msg[k] = wr::last_error();
       });
     for (auto& t : th) t.join();
   }
   for (int k = 0; k < n; ++k)
-    if (rc[k] != WR_OK) {
-      for (wr_context* x : ctx) wr_destroy(x);
-      return fail(rc[k], "device " + std::to_string(devices[k]) + ": " + msg[k]);
-    }
-  wr_context* c = ctx[0];
-  c->subs.assign(ctx.begin() + 1, ctx.end());
+    if (rc[k] != WR_OK) return fail(rc[k], "device " + std::to_string(devices[k]) + ": " + msg[k]);
+  ContextPtr c = std::move(ctx[0]);
+  for (int k = 1; k < n; ++k) c->subs.push_back(ctx[k].release());  // c owns them from here (wr_destroy)
   // RCCL communicators over the devices when they are distinct (a device
   // listed twice -- tests on one GPU -- sums by copies); WR_MULTI_REDUCE=peer
   // forces the copies
@@ -3532,19 +3401,13 @@ int wr_create_multi(const wr_scene* sc, const int* devices, int n, wr_context** 
   const char* mode = std::getenv("WR_MULTI_REDUCE");
   const bool want = !(mode && std::string(mode) == "peer");
   if (n > 1 && distinct && want) {
-    if (!rccl().ok) {
-      wr_destroy(c);
-      return fail(WR_E_HIP, rccl().why);
-    }
+    if (!rccl().ok) return fail(WR_E_HIP, rccl().why);
     std::vector<ncclComm_t> comms(n, nullptr);
     const ncclResult_t r = rccl().init_all(comms.data(), n, devices);
-    if (r != ncclSuccess) {
-      wr_destroy(c);
-      return fail(WR_E_HIP, std::string("ncclCommInitAll: ") + rccl().err_str(r));
-    }
+    if (r != ncclSuccess) return fail(WR_E_HIP, std::string("ncclCommInitAll: ") + rccl().err_str(r));
     c->dev_comms = comms;
   }
-  *out = c;
+  *out = c.release();
   return WR_OK;
 }
 

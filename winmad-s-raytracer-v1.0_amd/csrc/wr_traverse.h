@@ -2,7 +2,7 @@
 // (src/scene/KDtreeAccel.cpp:309-388) + Triangle::hit (src/geometry/triangle.cpp:22-87)
 // + Sphere::hit (src/geometry/sphere.cpp:17-78).
 //
-// Layout in HBM (built by wr_device.cpp from wr::Scene):
+// Layout in HBM (built by wr_flatten.cpp from wr::Scene):
 //   nodes  uint2 per node, pre-order (left child = node + 1):
 //            inner: x = split (float bits), y = right << 2 | axis (0..2)
 //            leaf : x = first ref,          y = count << 2 | 3
@@ -20,6 +20,7 @@
 #pragma once
 #include <type_traits>
 #include "wr_devmath.h"
+#include "wr_layout.h"
 
 namespace wrd {
 
@@ -250,18 +251,9 @@ struct TraceQueues {
 #define WR_PAIR_BATCH 256
 #endif
 constexpr int kPairBatch = WR_PAIR_BATCH;  // multiple of 256
-#ifndef WR_NODE_LEVELS
-// tree levels resolved per dependent record load (2, 3 or 4); 3 over 2: C2
-// 892 -> 911 Mrays/s; 4 (128-byte records, exact) loses 13-16 % on C2/C3
-#define WR_NODE_LEVELS 3
-#endif
+// WR_NODE_LEVELS (kRecLevels, kRecU4) and WR_LEAVES_PER_ROUND (kLeavesPerRound):
+// wr_layout.h, shared with the host flattening
 static_assert(kPairBatch % 256 == 0, "the owner-table scan covers 4 bytes per lane per 256 slots");
-static_assert(WR_NODE_LEVELS >= 2 && WR_NODE_LEVELS <= 4, "node record levels: 2, 3 or 4");
-constexpr int kRecLevels = WR_NODE_LEVELS < 3 ? 3 : WR_NODE_LEVELS;  // nrec3 layout
-constexpr int kRecU4 = kRecLevels == 4 ? 8 : 4;                      // uint4 per record
-#ifndef WR_LEAVES_PER_ROUND
-#define WR_LEAVES_PER_ROUND 4
-#endif
 // the walk of a round ends once every live lane holds WR_LEAVES_WAIT leaves
 // (lanes that get there first walk on, up to kLeavesPerRound).  With 3-level
 // node records and 16 pipelines, 1 beats 2 (C2 +1.8 %, C3 +0.9 %, VCM +1.7 %,
@@ -281,7 +273,6 @@ constexpr int kPairsInFlight = WR_PAIRS_IN_FLIGHT;
 constexpr int kPairsInFlightWide = WR_PAIRS_IN_FLIGHT_WIDE;
 static_assert(kPairBatch % (64 * kPairsInFlight) == 0 && kPairBatch % (64 * kPairsInFlightWide) == 0,
               "a batch is whole trips");
-constexpr int kLeavesPerRound = WR_LEAVES_PER_ROUND;
 #ifndef WR_RAY_GRAB
 #define WR_RAY_GRAB 128  // 64: C2 -0.8 %, 256: -1 %
 #endif
