@@ -142,9 +142,9 @@ typedef struct {
   int64_t verify_mismatches; /* (t, primitive) pairs that differ bit for bit      */
   int64_t pipelines;         /* render calls: the most concurrent pipelines one
                                 device ran (API v6)                              */
-  int64_t deferred_rays;     /* WR_TRACE_BVH BDPT: rays settled off the pipeline's
-                                critical path, their paths shaded a step later
-                                (deferred hard rays; API v6)        */
+  int64_t deferred_rays;     /* always 0: the experiment that counted here is
+                                removed; the field keeps the
+                                struct's layout (API v6)                         */
   int64_t bvh_width;         /* WR_TRACE_BVH: the search tree's width, 2 or 4 (4
                                 from 2^18 triangles); 0: KD walk
                                 (API v7)                                         */

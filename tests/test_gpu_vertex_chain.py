@@ -9,7 +9,7 @@ float, so every case here is a render against the oracle on the film gates of
 tests/_parity.py with equal ray counts -- on the smallest films at which the
 moved loads can go wrong: one wave, a partial last wave, tiled and untiled
 path orders, both connection sides, the sphere branch of a stored vertex's
-normal, pools that overflow (slot -1), the other schedules, and an emitter of
+normal, pools that overflow (slot -1), the sequential schedule, and an emitter of
 more than 32,768 faces (the stored vertex's material word, and a light table
 above the LDS cap).
 """
@@ -99,8 +99,8 @@ def test_full_pools_and_the_worst_case_layout(monkeypatch):
     _check(path, 32, 24, 2, 0, "chain_cbox32x24_i2_ctl0_nopools", full)
 
 
-# 4. the other schedules: sequential passes, deferred hard rays
-@pytest.mark.parametrize("env,val", [("WR_BDPT_OVERLAP", "0"), ("WR_DEFER", "1")])
+# 4. the other schedule: sequential passes
+@pytest.mark.parametrize("env,val", [("WR_BDPT_OVERLAP", "0")])
 def test_other_schedules(env, val, monkeypatch):
     path = _scenes.torus(24, 20)
     s = native.Scene(path)
@@ -116,8 +116,6 @@ def test_other_schedules(env, val, monkeypatch):
     base = render()
     monkeypatch.setenv(env, val)
     other = render()
-    if env == "WR_DEFER":
-        print(f"deferred rays: {other[1].deferred_rays}")
     _same(other, base)
     _check(path, 24, 20, 2, 0, f"chain_torus24x20_i2_ctl0_{env.lower()}{val}", other)
     _check(path, 24, 20, 2, 0, "chain_torus24x20_i2_ctl0_default", base)

@@ -139,3 +139,14 @@ def test_api_version_is_still_8():
     for name in ("wr_render_bdpt_moments", "wr_render_vcm_moments", "wr_render_path_moments", "wr_film_error"):
         assert hasattr(L, name), name
     assert C.sizeof(native.WrErrorInfo) == 40
+
+
+def test_wr_stats_keeps_its_v8_layout():
+    """wr_stats.deferred_rays counts nothing any more (always 0) and keeps its
+    place: 39 eight-byte fields, deferred_rays the 35th (include/winmad_rt.h as
+    of API v8: five counters, seconds, 2 x 8 per-category entries,
+    trace_wall_ms, then eleven counters in front of it and four behind)."""
+    assert C.sizeof(native.WrStats) == 312
+    assert native.WrStats.deferred_rays.offset == 272
+    assert native.WrStats.deferred_rays.size == 8
+    assert native.WrStats.bvh_width.offset == 280 and native.WrStats.redone.offset == 304

@@ -206,7 +206,7 @@ __device__ __forceinline__ void drst3(float* s, int p, int k, V3 v) {
 
 // Stored camera vertices of the overlapped schedule (BV_* records, slot
 // j * P + p, j < kCvMax): what connectVertices (:610-665) reads of the camera
-// side when a LATER light vertex of the path makes the connection.  Only
+// side when a later light vertex of the path makes the connection.  Only
 // vertices with length <= (maxlen - 2) / 2 can meet a later light vertex
 // (c < l and l + 1 + c <= maxlen), so kCvMax = 4 slots for maxlen <= 10.
 constexpr int kCvMax = (kVMax + 1 - 2) / 2;
@@ -536,9 +536,9 @@ __device__ __forceinline__ VtxIn vertex_inputs(const BdptArgs& A, bool on, int p
 }
 
 // One light-subpath vertex (:77-128): path p's ray (o, d) hit prim at t
-// (prim < 0: a miss, or a pending hard ray -- nothing to do).  Every lane of
-// the wave calls it (queue appends).  oslot: the step whose queue gets the
-// extension ray -- slot + 1, or slot + 2 for a deferred vertex (k_late_light).
+// (prim < 0: a miss -- nothing to do).  Every lane of the wave calls it
+// (queue appends).  oslot: the step whose queue gets the extension ray
+// (slot + 1).
 __device__ __forceinline__ void light_vertex(const BdptArgs& A, const DMat* mats, const VtxIn& in, int oslot) {
   const BdptBuf& B = A.B;
   const DevScene& S = A.S;
@@ -700,26 +700,16 @@ __device__ __forceinline__ void light_vertex(const BdptArgs& A, const DMat* mats
   }
 }
 
-template <bool CAMERA>
-__device__ __forceinline__ void late_vertex_body(const BdptArgs& A, const DMat* mats, const DLight* lights,
-                                                 const LateList& LL, const int* cnt, int slot, int bid, int nblk);
-// Blocks [0, gridDim.x - nlate) shade this step's vertices, the last nlate
-// blocks the previous step's deferred ones (late_vertex_body).
 template <bool GT>
-__global__ void __launch_bounds__(kShadeBlock) WR_SHADE_OCC k_light_shade(BdptGroup G_, int slot, LateArgs L,
-                                                                         int nlate) {
+__global__ void __launch_bounds__(kShadeBlock) WR_SHADE_OCC k_light_shade(BdptGroup G_, int slot) {
   const BdptArgs& A = G_.a[blockIdx.y];
   WR_BDPT_TABLES(A)
-  const int nmain = static_cast<int>(gridDim.x) - nlate;
-  if (static_cast<int>(blockIdx.x) >= nmain) {
-    late_vertex_body<false>(A, mats, lights, L.l[blockIdx.y], L.n[blockIdx.y], slot, blockIdx.x - nmain, nlate);
-    return;
-  }
+  (void)lights;
   const BdptBuf& B = A.B;
   const int cur = slot & 1;
   const int n = A.sc->ext[slot];
   if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&A.ctr->closest, (unsigned long long)n);
-  const int gstride = nmain * blockDim.x;
+  const int gstride = gridDim.x * blockDim.x;
   const int nround = (n + gstride - 1) / gstride * gstride;  // whole waves reach the appends
   for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < nround; j += gstride) {
     // stage A: the entry's columns, all at once (a lane past the end reads the
@@ -800,14 +790,13 @@ __global__ void __launch_bounds__(kShadeBlock) WR_NO_PK_FP32 k_camera_gen(BdptGr
 
 // One camera-subpath vertex (:148-260): emitter hit, DI setup, vertex
 // connections (shadow rays queued), scattering -- path p's ray (o, d) hit prim
-// at t (prim < 0: a miss, or a pending hard ray: nothing).  Every lane of the
-// wave calls it.  oslot: the step whose queues (shadow / aux, DI records,
-// extension) get this vertex's rays -- slot + 1, or slot + 2 for a deferred
-// vertex (k_late_camera).
+// at t (prim < 0: a miss: nothing).  Every lane of the wave calls it.  oslot:
+// the step whose queues (shadow / aux, DI records, extension) get this
+// vertex's rays (slot + 1).
 // ebase: the queue index of the camera pass's first extension ray of step
 // oslot (cam_ext_base, read once by the caller)
 __device__ __forceinline__ void camera_vertex(const BdptArgs& A, const DMat* mats, const DLight* lights,
-                                              const VtxIn& in, int oslot, int ebase = 0) {
+                                              const VtxIn& in, int oslot, int ebase) {
   const BdptBuf& B = A.B;
   const DevScene& S = A.S;
   const int P = B.P, nxt = oslot & 1, cap = B.cap_sq;  // P: buffer stride
@@ -1032,32 +1021,6 @@ __device__ __forceinline__ void camera_shade_body(const BdptArgs& A, const DMat*
   }
 }
 
-// Deferred vertices (WR_TRACE_BVH, "deferred hard rays" in wr_render.hip):
-// the paths whose step-(slot - 1) hit was settled off the critical path (by
-// the blocks of step slot's search launch) are shaded one step late, by extra
-// blocks of step slot's vertex launch, into the same queues as this step's
-// vertices (step slot + 1).  Light vertices feed only their own path's camera
-// connections (:130, :222-229) and every path keeps its own state, counters
-// and random numbers, so the film is the one of the undeferred render.
-template <bool CAMERA>
-__device__ __forceinline__ void late_vertex_body(const BdptArgs& A, const DMat* mats, const DLight* lights,
-                                                 const LateList& LL, const int* cnt, int slot, int bid, int nblk) {
-  const int half = LL.cap >> 1;
-  const int nt = min(cnt[0], half), n = nt + min(cnt[1], half);
-  const int gstride = nblk * blockDim.x;
-  const int nround = (n + gstride - 1) / gstride * gstride;
-  for (int j = bid * blockDim.x + threadIdx.x; j < nround; j += gstride) {
-    // (a lane past the end reads the last record; n > 0 here)
-    const int jc = min(j, n - 1), i = jc < nt ? jc : half + (jc - nt);
-    const int p = LL.pth[i], prim = LL.prim[i];
-    const float t = LL.t[i];
-    const V3 o = ld3(LL.o3, LL.cap, i), d = ld3(LL.d3, LL.cap, i);
-    const VtxIn in = vertex_inputs<CAMERA>(A, j < n, p, prim, t, o, d);
-    if (CAMERA) camera_vertex(A, mats, lights, in, slot + 1);
-    else light_vertex(A, mats, in, slot + 1);
-  }
-}
-
 // Light-tracing splats and camera-pass shadow / aux rays after traversal.
 // Light-tracing splats and camera-pass shadow / aux rays of step `slot` after
 // traversal.  A DI record is finalized (getDirectIllumination's combination,
@@ -1138,18 +1101,15 @@ __device__ __forceinline__ void sq_resolve_body(const BdptArgs& A, int slot, int
 // One camera-pass step after its traversal: resolve the step's shadow / aux
 // rays (blocks [0, nres)) and shade its camera vertices (the rest) -- they touch
 // different queue / DI buffers.  The last step has no vertices (shade = 0).
-// ... blocks [0, nres) resolve, then this step's vertices, then (the last
-// nlate blocks) the previous step's deferred vertices.
 template <bool GT>
 __global__ void __launch_bounds__(kShadeBlock) WR_SHADE_OCC k_camera_step(BdptGroup G_, int slot, int nres,
-                                                                         int shade, LateArgs L, int nlate) {
+                                                                         int shade) {
   const BdptArgs& A = G_.a[blockIdx.y];
-  const int b = static_cast<int>(blockIdx.x), nmain = static_cast<int>(gridDim.x) - nlate;
+  const int b = static_cast<int>(blockIdx.x), nblk = static_cast<int>(gridDim.x);
   if (b < nres) {  // (block-uniform: the resolve reads neither table)
     sq_resolve_body(A, slot, b, nres);
     return;
   }
   WR_BDPT_TABLES(A)
-  if (b >= nmain) late_vertex_body<true>(A, mats, lights, L.l[blockIdx.y], L.n[blockIdx.y], slot, b - nmain, nlate);
-  else if (shade) camera_shade_body(A, mats, lights, slot, b - nres, nmain - nres);
+  if (shade) camera_shade_body(A, mats, lights, slot, b - nres, nblk - nres);
 }

@@ -303,7 +303,7 @@ __device__ __forceinline__ bool cell_may_be_reached(uint4 h0, uint4 h1, V3 o, V3
   return !(tn > tf);  // NaN: kept
 }
 
-// The membership replays (kd_member, scan_rays) skip leaves whose cell the
+// The membership replays (kd_member, scan_fast) skip leaves whose cell the
 // ray's line misses, as the tie resolution does (WR_SCAN_CELL_FILTER=0: off).
 #ifndef WR_SCAN_CELL_FILTER
 #define WR_SCAN_CELL_FILTER 1
@@ -1921,7 +1921,6 @@ __device__ __forceinline__ void resolve_fast(const DevScene& S, const FastScene&
     bool need = false, scan = false, big_tie = false, walk = false, pair_tie = false, lane_pair = false;
     int q = 0, r = 0, p1 = -1;
     float t1 = WR_INF;
-    V3 o = v3(0.f, 0.f, 0.f), d = v3(0.f, 0.f, 0.f);
     if (idx < QI.n) {
       QI.locate(idx, q, r);
       // every load that does not depend on p1 in flight at once
@@ -1933,8 +1932,8 @@ __device__ __forceinline__ void resolve_fast(const DevScene& S, const FastScene&
       const float* d3 = qfield(Q, q, [](const RayQueue& x) { return x.d3; });
       const int cap = qfield(Q, q, [](const RayQueue& x) { return x.cap; });
       const float* tmx = qfield(Q, q, [](const RayQueue& x) { return x.tmax; });
-      o = v3(o3[r], o3[cap + r], o3[2 * cap + r]);
-      d = v3(d3[r], d3[cap + r], d3[2 * cap + r]);
+      const V3 o = v3(o3[r], o3[cap + r], o3[2 * cap + r]);
+      const V3 d = v3(d3[r], d3[cap + r], d3[2 * cap + r]);
       const float rtmax = tmx ? tmx[r] : WR_INF;
       // p1's membership record: one line with its first four leaves' cells
       const float4* pr = F.prim_rec + 8 * static_cast<size_t>(max(p1, 0));
@@ -1985,38 +1984,6 @@ __device__ __forceinline__ void resolve_fast(const DevScene& S, const FastScene&
               ctr.mem_sum += dt;
               ctr.scans += (ln > 4 && steps > 64) ? 1u : 0u;
             }
-          }
-        }
-      }
-    }
-    // a deferrable queue (BDPT extension rays): the ray goes to the queue's
-    // late list -- settled off the pipeline's critical path, its path shaded
-    // one step later -- unless its path was deferred before in this pass.
-    // Rare (0.1-0.5 % of rays): one atomic per listed ray.
-    if ((need || scan) && !walk) {
-      const LateList* LL = qfield(Q, q, [](const RayQueue& x) { return x.late; });
-      if (LL) {
-        const int pth = LL->path[r];
-        const int bit = qfield(Q, q, [](const RayQueue& x) { return x.late_bit; });
-        if (!(LL->delayed[pth] & bit)) {
-          const int half = LL->cap >> 1;
-          const int k = atomicAdd(qfield(Q, q, [](const RayQueue& x) { return x.late_n; }) + (scan ? 1 : 0), 1);
-          if (k < half) {
-            const int i = scan ? half + k : k;
-            const int lc = LL->cap;
-            LL->o3[i] = o.x;
-            LL->o3[lc + i] = o.y;
-            LL->o3[2 * lc + i] = o.z;
-            LL->d3[i] = d.x;
-            LL->d3[lc + i] = d.y;
-            LL->d3[2 * lc + i] = d.z;
-            LL->t1[i] = t1;
-            LL->p1[i] = p1;
-            LL->pth[i] = pth;
-            LL->tie[i] = big_tie ? 1 : 0;
-            LL->delayed[pth] = static_cast<uint8_t>(LL->delayed[pth] | bit);
-            qfield(Q, q, [](const RayQueue& x) { return x.out_prim; })[r] = kPendingPrim;
-            need = scan = false;
           }
         }
       }
@@ -2250,15 +2217,20 @@ __device__ __forceinline__ void pair_fast(const DevScene& S, const FastScene& F,
 // leaf's cell, else the replay of its path -- and stop once one is reached;
 // p1 then stands.  If none is, t1's triangle is not visited and the ray is
 // settled in general by the same wave (settle_ray, one ray per wave).
-template <bool COUNT, class Get>
-__device__ __forceinline__ void scan_rays(const DevScene& S, const FastScene& F, int ns, Get get, int bid, int nb,
-                                          uint32_t* lds, FastCounters& ctr) {
+template <bool COUNT>
+__device__ __forceinline__ void scan_fast(const DevScene& S, const FastScene& F, const TraceQueues& Q,
+                                          const int* hard, const int* hard_n, int hcap, int bid, int nb, uint32_t* lds,
+                                          FastCounters& ctr) {
   const int lane = __lane_id();
   int* stk_node = reinterpret_cast<int*>(lds) + lane;
   float* stk_tmin = reinterpret_cast<float*>(lds) + F.depth * 64 + lane;
+  const QueueIndex QI(Q);
+  const int ns = (F.diag & (32 | 64)) ? 0 : hard_n[1];
   for (int i = bid; i < ns; i += nb) {
-    bool tie = false;  // a near-tie on a many-leaf primitive: straight to the general resolution
-    const ListedRay L = get(i, tie);
+    const int e = hard[hcap - 1 - i];
+    const bool tie = e < 0;  // a near-tie on a many-leaf primitive: straight to the general resolution
+    ListedRay L = listed_ray(Q, QI, tie ? ~e : e);
+    if (tie && !F.diag && F.pair > 0) L.pair = reinterpret_cast<const int2*>(hard + hcap)[~e];  // (kPairWindow)
     bool member = false;
     float tmin, tmax;
     uint32_t steps = 0;
@@ -2306,7 +2278,7 @@ __device__ __forceinline__ void scan_rays(const DevScene& S, const FastScene& F,
       if (lane == 0) ctr.scan_t += static_cast<uint32_t>(wall_clock64() - s0);
 #endif
     }
-    if (member) {  // p1 stands (a queue entry holds it already; a late record gets it)
+    if (member) {  // p1 stands (the queue entry holds it already)
       if (lane == 0) {
         L.outt[L.r] = L.t1;
         L.outp[L.r] = L.p1;
@@ -2315,60 +2287,6 @@ __device__ __forceinline__ void scan_rays(const DevScene& S, const FastScene& F,
     }
     settle_ray<COUNT, true>(S, F, L.o, L.d, L.rtmin, L.rtmax, L.t1, stk_node, stk_tmin, L.outt, L.outp, L.r,
                             lane == 0, ctr, false, nullptr, L.p1, L.pair);
-  }
-}
-template <bool COUNT>
-__device__ __forceinline__ void scan_fast(const DevScene& S, const FastScene& F, const TraceQueues& Q,
-                                          const int* hard, const int* hard_n, int hcap, int bid, int nb, uint32_t* lds,
-                                          FastCounters& ctr) {
-  const QueueIndex QI(Q);
-  const int ns = (F.diag & (32 | 64)) ? 0 : hard_n[1];
-  scan_rays<COUNT>(S, F, ns, [&](int i, bool& tie) {
-    const int e = hard[hcap - 1 - i];
-    tie = e < 0;
-    ListedRay L = listed_ray(Q, QI, tie ? ~e : e);
-    if (tie && !F.diag && F.pair > 0) L.pair = reinterpret_cast<const int2*>(hard + hcap)[~e];  // (kPairWindow)
-    return L;
-  }, bid, nb, lds, ctr);
-}
-
-// A record of a late list (extension rays only: [0, inf) windows).
-__device__ __forceinline__ ListedRay late_ray(const LateList& LL, int i) {
-  ListedRay L;
-  const int c = LL.cap;
-  L.o = v3(LL.o3[i], LL.o3[c + i], LL.o3[2 * c + i]);
-  L.d = v3(LL.d3[i], LL.d3[c + i], LL.d3[2 * c + i]);
-  L.rtmin = 0.f;
-  L.rtmax = WR_INF;
-  L.t1 = LL.t1[i];
-  L.p1 = LL.p1[i];
-  L.r = i;
-  L.outt = LL.t;
-  L.outp = LL.prim;
-  L.walk = false;
-  L.pair = make_int2(-1, 0);
-  return L;
-}
-// k_late_hard: a late list's tie entries (blocks [0, hard_blocks): one per
-// wave up to wave_max entries, else one per lane on lane_blocks) and scan
-// entries (the other blocks, one per wave).  Same resolutions as k_fast_hard.
-template <bool COUNT>
-__device__ __forceinline__ void late_hard(const DevScene& S, const FastScene& F, const LateList& LL, const int* n,
-                                          int b, int nb, int hard_blocks, int lane_blocks, int wave_max,
-                                          uint32_t* lds, FastCounters& ctr) {
-  const int half = LL.cap >> 1;
-  const int nt = min(n[0], half), ns = min(n[1], half);
-  if (b < hard_blocks) {
-    auto get = [&](int i) { return late_ray(LL, i); };
-    if (nt <= wave_max)
-      hard_rays<COUNT, true>(S, F, nt, get, b, hard_blocks, lds, ctr);
-    else if (b < lane_blocks)
-      hard_rays<COUNT, false>(S, F, nt, get, b, lane_blocks, lds, ctr);
-  } else {
-    scan_rays<COUNT>(S, F, ns, [&](int i, bool& tie) {
-      tie = LL.tie[half + i] != 0;
-      return late_ray(LL, half + i);
-    }, b - hard_blocks, nb - hard_blocks, lds, ctr);
   }
 }
 
@@ -2396,28 +2314,6 @@ __device__ __forceinline__ void verify_fast(const DevScene& S, const FastScene& 
     kd_walk<false>(S, o, d, tmn ? tmn[r] : 0.f, tmx ? tmx[r] : WR_INF, stk_node, stk_tmin, tb, pb, dummy);
     const int p = qfield(Q, q, [](const RayQueue& x) { return x.out_prim; })[r];
     const float t = qfield(Q, q, [](const RayQueue& x) { return x.out_t; })[r];
-    if (p == kPendingPrim) continue;  // deferred: checked by verify_late
-    ++rays;
-    if (p != pb || (pb >= 0 && __float_as_uint(t) != __float_as_uint(tb))) ++bad;
-  }
-}
-// The same check for a late list's records (after k_late_hard).
-__device__ __forceinline__ void verify_late(const DevScene& S, const FastScene& F, const LateList& LL, const int* n,
-                                            uint32_t* lds, uint32_t& rays, uint32_t& bad) {
-  const int lane = __lane_id();
-  int* stk_node = reinterpret_cast<int*>(lds) + lane;
-  float* stk_tmin = reinterpret_cast<float*>(lds) + F.depth * 64 + lane;
-  FastCounters dummy{};
-  const int half = LL.cap >> 1;
-  const int nt = min(n[0], half), nall = nt + min(n[1], half);
-  for (int j = blockIdx.x * 64 + lane; j < nall; j += gridDim.x * 64) {
-    const int i = j < nt ? j : half + (j - nt);
-    const ListedRay L = late_ray(LL, i);
-    float tb;
-    int pb;
-    kd_walk<false>(S, L.o, L.d, L.rtmin, L.rtmax, stk_node, stk_tmin, tb, pb, dummy);
-    const int p = LL.prim[i];
-    const float t = LL.t[i];
     ++rays;
     if (p != pb || (pb >= 0 && __float_as_uint(t) != __float_as_uint(tb))) ++bad;
   }

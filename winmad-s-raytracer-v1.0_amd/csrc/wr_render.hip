@@ -124,12 +124,6 @@ constexpr int kShadeBlock = 256;
 #endif
 constexpr int kGroup = WR_GROUP;
 
-// The late lists of one pipeline step (deferred hard rays, one per group member)
-struct LateArgs {
-  LateList l[kGroup];
-  int* n[kGroup];
-};
-
 enum SqKind { SQ_SPLAT = 0, SQ_CONN = 1, SQ_NEE = 2, SQ_DIB = 3 };
 enum DiFlag { DI_NEE = 1, DI_BSDF = 2, DI_EARLY = 4 };
 // DI record state word: rays still to resolve (low byte) | results
@@ -150,7 +144,6 @@ struct StepCounters {
   int mq[kSlots];     // VCM: merge queries queued at step `slot`
   int hard[kSlots][3];  // WR_TRACE_BVH: rays of step `slot` left to k_fast_hard (tie list, scan list, pair list)
   int rlist[kSlots];    // WR_TRACE_BVH: rays of step `slot` the search left to k_fast_resolve
-  int late[kSlots][2];  // WR_TRACE_BVH: rays of step `slot` deferred (late list: ties, scans)
   int vpool, cpool;     // BDPT, overlapped: records taken from the light / camera vertex pools
 };
 struct DevCounters {
@@ -162,7 +155,6 @@ struct DevCounters {
   unsigned long long vm_queries, vm_found, vm_merged;  // VCM range queries / vertices in radius / merges
   unsigned long long bvh_nodes, bvh_tests, kd_replay, fallback;  // WR_TRACE_BVH work (count_work)
   unsigned long long verify_rays, verify_bad;                   // WR_BVH_VERIFY
-  unsigned long long deferred;  // BDPT rays settled off the critical path (late lists)
   unsigned long long lat[12];  // WR_TRACE_BVH latency tail (FastCounters mem_max .. scans; max or sum; tie_col .. tie_pass2)
   unsigned long long ww[4];   // kd_walk_wave: walks, rounds, nodes, serial fall-backs
   unsigned long long overflow;  // BDPT: appends a full vertex pool / shadow queue dropped (the render is redone)
@@ -306,9 +298,6 @@ __device__ __forceinline__ void fast_counts(DevCounters* ctr, const FastCounters
 #ifndef WR_FAST_WAVES
 #define WR_FAST_WAVES 4  // minimum waves per SIMD the search's registers must allow
 #endif
-// LATE: blocks [0, lblocks) settle the previous step's deferred hard rays
-// (its late lists, late_hard) beside this step's search; they come first so
-// that they are dispatched with the search's persistent blocks, not after them
 // W: the search tree's width (FastScene::wide)
 #ifndef WR_FAST4_WAVES
 #define WR_FAST4_WAVES 5  // the 4-wide search: 98 VGPRs at 4, held to 96 for 5 waves per SIMD
@@ -317,45 +306,32 @@ __device__ __forceinline__ void fast_counts(DevCounters* ctr, const FastCounters
 // that the triangle scenes' search keeps its registers
 // RL: the search settles the rays whose winner's membership its first leaf
 // cells prove (the resolve's first test) and lists the rest for k_fast_resolve
-template <bool COUNT, bool LATE, int W, bool SPH, bool RL = false>
+template <bool COUNT, int W, bool SPH, bool RL = false>
 __global__ void __launch_bounds__(kTraceBlock)
-__attribute__((amdgpu_waves_per_eu(W == 4 && !LATE ? WR_FAST4_WAVES : WR_FAST_WAVES, 8))) WR_NO_PK_FP32
+__attribute__((amdgpu_waves_per_eu(W == 4 ? WR_FAST4_WAVES : WR_FAST_WAVES, 8))) WR_NO_PK_FP32
 k_trace_fast(DevScene S, FastScene F, TraceQueues Q, DevCounters* ctr, int* fetch, float* t2buf, int2* pairs,
-             int2* spill, LateArgs L, int lblocks, int gn, int hblocks, int lane_blocks, int wave_max, int* rlist,
-             int* rlist_n) {
+             int2* spill, int* rlist, int* rlist_n) {
   extern __shared__ uint32_t smem[];
   FastCounters fc{};
-  const int b = static_cast<int>(blockIdx.x);
-  if (LATE && b < lblocks) {
-    const int per = lblocks / gn, m = b / per, bb = b % per;
-    late_hard<COUNT>(S, F, L.l[m], L.n[m], bb, per, hblocks, lane_blocks, wave_max, smem, fc);
-    if (bb == 0 && threadIdx.x == 0) {
-      const int half = L.l[m].cap >> 1;
-      atomicAdd(&ctr->deferred, static_cast<unsigned long long>(min(L.n[m][0], half) + min(L.n[m][1], half)));
-    }
-  } else {
-    trace_fast<COUNT, W, SPH, RL>(S, F, Q, fetch, t2buf, pairs, spill, smem, fc, b - (LATE ? lblocks : 0),
-                                  static_cast<int>(gridDim.x) - (LATE ? lblocks : 0), rlist, rlist_n);
-  }
+  trace_fast<COUNT, W, SPH, RL>(S, F, Q, fetch, t2buf, pairs, spill, smem, fc, static_cast<int>(blockIdx.x),
+                                static_cast<int>(gridDim.x), rlist, rlist_n);
   if (COUNT) fast_counts<COUNT>(ctr, fc);
 }
 // the search kernel for a tree width (instantiated for 2 and 4; 8 when the
 // library is built with WR_BVH_WIDE=8)
 // RL: the search's per-wave buffer of listed rays (trace_fast)
 constexpr size_t kRlistLds = 64 * sizeof(int);
-using TraceFastKernel = void (*)(DevScene, FastScene, TraceQueues, DevCounters*, int*, float*, int2*, int2*, LateArgs,
-                                 int, int, int, int, int, int*, int*);
-template <bool COUNT, bool LATE>
+using TraceFastKernel = void (*)(DevScene, FastScene, TraceQueues, DevCounters*, int*, float*, int2*, int2*, int*,
+                                 int*);
+template <bool COUNT>
 TraceFastKernel trace_fast_kernel(int wide, bool sph = false, bool rl = false) {
 #if WR_BVH_WIDE == 8
-  if (wide == 8) return k_trace_fast<COUNT, LATE, 8, false>;  // (triangle scenes: the 8-wide tree is a build option)
+  if (wide == 8) return k_trace_fast<COUNT, 8, false>;  // (triangle scenes: the 8-wide tree is a build option)
 #endif
-  // (the deferred-hard-ray variants, LATE, are not built with spheres: defer_enabled)
-  if (sph && !LATE) return wide == 4 ? k_trace_fast<COUNT, false, 4, true> : k_trace_fast<COUNT, false, 2, true>;
-  // (the resolve list: triangle trees, no late lists)
-  if (rl && !LATE)
-    return wide == 4 ? k_trace_fast<COUNT, false, 4, false, true> : k_trace_fast<COUNT, false, 2, false, true>;
-  return wide == 4 ? k_trace_fast<COUNT, LATE, 4, false> : k_trace_fast<COUNT, LATE, 2, false>;
+  if (sph) return wide == 4 ? k_trace_fast<COUNT, 4, true> : k_trace_fast<COUNT, 2, true>;
+  // (the resolve list: triangle trees)
+  if (rl) return wide == 4 ? k_trace_fast<COUNT, 4, false, true> : k_trace_fast<COUNT, 2, false, true>;
+  return wide == 4 ? k_trace_fast<COUNT, 4, false> : k_trace_fast<COUNT, 2, false>;
 }
 #ifndef WR_RESOLVE_WAVES
 #define WR_RESOLVE_WAVES 0  // > 0: the resolve's register budget as waves per SIMD (0: the compiler's choice, 101 VGPRs)
@@ -414,19 +390,6 @@ k_fast_hard(DevScene S, FastScene F, TraceQueues Q, DevCounters* ctr, const int*
     scan_fast<COUNT>(S, F, Q, hard, hard_n, hcap, b - s0, static_cast<int>(gridDim.x) - s0, smem, fc);
   }
   if (COUNT) fast_counts<COUNT>(ctr, fc);
-}
-
-// WR_BVH_VERIFY: the late lists' answers against the KD walk
-__global__ void __launch_bounds__(kTraceBlock) WR_NO_PK_FP32
-k_late_verify(DevScene S, FastScene F, LateArgs L, DevCounters* ctr) {
-  extern __shared__ uint32_t smem[];
-  uint32_t rays = 0, bad = 0;
-  verify_late(S, F, L.l[blockIdx.y], L.n[blockIdx.y], smem, rays, bad);
-  const unsigned long long a = wave_sum(rays), b = wave_sum(bad);
-  if (lane_id() == 0) {
-    atomicAdd(&ctr->verify_rays, a);
-    atomicAdd(&ctr->verify_bad, b);
-  }
 }
 
 __global__ void __launch_bounds__(kTraceBlock) WR_NO_PK_FP32
@@ -654,13 +617,6 @@ struct Pipe {
   std::vector<int> ev_cat;
   size_t ev_used = 0;
   hipEvent_t done = nullptr;
-  // deferred hard rays (BDPT, WR_TRACE_BVH): a step's late lists, settled and
-  // shaded by extra blocks of the next step's launches
-  Arena late_mem;
-  size_t late_recs = 0, late_paths = 0;  // records per list, paths per member laid out
-  LateList late_h[kGroup][2]{};          // host copies: [member][step parity]
-  LateList* late_d = nullptr;            // device copies, same order
-  uint8_t* delayed = nullptr;            // [kGroup][late_paths]
   // moments renders only (wr_render_*_moments): the films of the passes this
   // pipeline has open, zero between passes (k_film_fold clears what it folds)
   DevBuf<float> mom[kGroup];
@@ -747,8 +703,6 @@ struct wr_context {
   int resolve_blocks = 0; // k_fast_resolve's one-wave workgroups (0: fast_blocks; env WR_RESOLVE_GRID per CU)
   bool resolve_list = true;  // the search lists the rays the resolve must see (env WR_RESOLVE_LIST=0: all rays)
   bool verify = false;      // WR_BVH_VERIFY=1: every BVH answer checked against the KD walk
-  // BDPT hard rays off the critical path (env WR_DEFER=1; off by default)
-  int defer = -1;
   // BDPT light and camera passes overlapped (wr_bdpt.h; env WR_BDPT_OVERLAP=0: sequential)
   bool bdpt_overlap = true;
   DevBuf<float> api_t2;    // t2 scratch of the API path (5 floats per ray, as Pipe::t2buf)
@@ -1182,10 +1136,10 @@ struct Timer {
   }
 };
 
+// (count2: set by the one caller that has it, the overlapped BDPT schedule)
 RayQueue rq(const float* o3, const float* d3, int cap, const int* cnt, float* t, int* prim,
-            const float* tmin = nullptr, const float* tmax = nullptr, const float* cut = nullptr,
-            const LateList* late = nullptr, int* late_n = nullptr, int late_bit = 0, const int* cnt2 = nullptr) {
-  return RayQueue{o3, d3, cap, cnt, tmin, tmax, t, prim, cut, late, late_n, late_bit, cnt2};
+            const float* cut = nullptr, const float* tmin = nullptr, const float* tmax = nullptr) {
+  return RayQueue{o3, d3, cap, cnt, tmin, tmax, t, prim, cut, nullptr};
 }
 // a queue's ray count read back to the host (diagnostics only: synchronous)
 int host_count(const RayQueue& q) {
@@ -1295,59 +1249,10 @@ int ensure_t2(wr_context* c, Pipe& p, size_t rays) {
   return p.t2buf.grow(5 * rays);  // t2 / list, hard lists, pair records (int2), pair list
 }
 
-// Late lists of a pipeline (deferred hard rays), `recs` records each, for
-// buffer sets of `paths` paths.  The lists' queue path arrays are the
-// pipeline's current BDPT buffers.
-int ensure_late(Pipe& p, int paths, int recs) {
-  if (p.late_recs < static_cast<size_t>(recs) || p.late_paths < static_cast<size_t>(paths)) {
-    recs = std::max<int>(recs, static_cast<int>(p.late_recs));
-    paths = std::max<int>(paths, static_cast<int>(p.late_paths));
-    auto lay = [&](Arena& a, bool set) {
-      for (int m = 0; m < kGroup; ++m)
-        for (int k = 0; k < 2; ++k) {
-          LateList L{};
-          L.cap = recs;
-          L.o3 = a.take<float>(3 * size_t(recs));
-          L.d3 = a.take<float>(3 * size_t(recs));
-          L.t1 = a.take<float>(recs);
-          L.p1 = a.take<int>(recs);
-          L.pth = a.take<int>(recs);
-          L.tie = a.take<int>(recs);
-          L.t = a.take<float>(recs);
-          L.prim = a.take<int>(recs);
-          if (set) p.late_h[m][k] = L;
-        }
-      uint8_t* dl = a.take<uint8_t>(size_t(kGroup) * paths);
-      LateList* ld = a.take<LateList>(size_t(kGroup) * 2);
-      if (set) {
-        p.delayed = dl;
-        p.late_d = ld;
-      }
-    };
-    if (int rc = p.late_mem.reserve(measure([&](Arena& a) { lay(a, false); }))) return rc;
-    lay(p.late_mem, true);
-    p.late_recs = recs;
-    p.late_paths = paths;
-  }
-  for (int m = 0; m < kGroup; ++m)
-    for (int k = 0; k < 2; ++k) {
-      LateList& L = p.late_h[m][k];
-      L.path = p.bb[m].q_path[k];
-      L.delayed = p.delayed + size_t(m) * p.late_paths;
-    }
-  HIPCHK(hipMemcpyAsync(p.late_d, p.late_h, sizeof(p.late_h), hipMemcpyHostToDevice, p.stream));
-  return WR_OK;
-}
-
 // One persistent traversal launch over the queues of Q (max_rays bounds the
 // grid).  WR_TRACE_BVH: the verified-BVH search + its resolve launch instead.
-// Blocks of a fused search launch that settle the previous step's late lists:
-// per group member kLateTieBlocks tie waves (one tie per wave up to that many,
-// else one per lane on kLateLaneBlocks) and kLateScanBlocks scan waves
-constexpr int kLateTieBlocks = 256, kLateLaneBlocks = 64, kLateScanBlocks = 64;
 int trace_launch(wr_context* c, hipStream_t stream, DevCounters* ctr, const TraceSlot& ts, Timer& tm, bool count,
-                 const TraceQueues& Q_, int max_rays, int mode = TRACE_PLAIN, bool hard_wave = false,
-                 const LateArgs* late_prev = nullptr, int late_gn = 0) {
+                 const TraceQueues& Q_, int max_rays, int mode = TRACE_PLAIN, bool hard_wave = false) {
   int* fetch = ts.fetch;
   TraceQueues Q = Q_;
   if (c->no_cut)  // measurement knob: the same launches without the dead-work elision
@@ -1361,7 +1266,7 @@ int trace_launch(wr_context* c, hipStream_t stream, DevCounters* ctr, const Trac
     // the rest for the resolve (in the t2 region: t2 is kept by diagnostics
     // only).  Measured (profiles/r5/resolve_list): C4 +5 %, C2 +1 %, VCM +1 %;
     // PT's dense launches -0.8 %, so they keep the resolve over every ray
-    const bool rl = c->resolve_list && !F.diag && !late_prev && !F.sph && F.wide != 8 && mode != TRACE_DENSE;
+    const bool rl = c->resolve_list && !F.diag && !F.sph && F.wide != 8 && mode != TRACE_DENSE;
     int* rlist = rl ? reinterpret_cast<int*>(ts.t2) : nullptr;
     int* rlist_n = rl ? ts.rlist_n : nullptr;
     const size_t rlds = slds + (rl ? kRlistLds : 0);
@@ -1375,22 +1280,9 @@ int trace_launch(wr_context* c, hipStream_t stream, DevCounters* ctr, const Trac
       (void)hipEventCreate(&fb);
       (void)hipEventRecord(f0, stream);
     }
-    if (late_prev) {  // + the previous step's deferred hard rays, beside the search
-      const int lblocks = late_gn * (kLateTieBlocks + kLateScanBlocks);
-      auto kf = count ? trace_fast_kernel<true, true>(F.wide, F.sph) : trace_fast_kernel<false, true>(F.wide, F.sph);
-      hipLaunchKernelGGL(kf, dim3(lblocks + fgrid),
-                         dim3(kTraceBlock), std::max(slds, lds), stream, c->ds, F, Q, ctr, fetch, ts.t2, pairs, ts.spill,
-                         *late_prev, lblocks, late_gn, kLateTieBlocks, kLateLaneBlocks, kLateTieBlocks, nullptr, nullptr);
-      if (c->verify)
-        hipLaunchKernelGGL(k_late_verify, dim3(64, late_gn), dim3(kTraceBlock), lds, stream, c->ds, F, *late_prev,
-                           ctr);
-    } else {
-      auto kf = count ? trace_fast_kernel<true, false>(F.wide, F.sph, rl)
-                      : trace_fast_kernel<false, false>(F.wide, F.sph, rl);
-      hipLaunchKernelGGL(kf, dim3(fgrid),
-                         dim3(kTraceBlock), rlds, stream, c->ds, F, Q, ctr, fetch, ts.t2, pairs, ts.spill, LateArgs{}, 0,
-                         1, 0, 0, 0, rlist, rlist_n);
-    }
+    auto kf = count ? trace_fast_kernel<true>(F.wide, F.sph, rl) : trace_fast_kernel<false>(F.wide, F.sph, rl);
+    hipLaunchKernelGGL(kf, dim3(fgrid), dim3(kTraceBlock), rlds, stream, c->ds, F, Q, ctr, fetch, ts.t2, pairs,
+                       ts.spill, rlist, rlist_n);
     if (c->trace_log) (void)hipEventRecord(fa, stream);
     int* hard = reinterpret_cast<int*>(ts.t2 + ts.t2_cap);
     hipLaunchKernelGGL(count ? k_fast_resolve<true> : k_fast_resolve<false>,
@@ -1636,7 +1528,6 @@ int finish_render(wr_context* c, int n, wr_stats* st, double t0_host, unsigned l
     sum.fallback += h.fallback;
     sum.verify_rays += h.verify_rays;
     sum.verify_bad += h.verify_bad;
-    sum.deferred += h.deferred;
     for (int k = 0; k < 8; ++k) sum.stamps[k] += h.stamps[k];
   }
   st->closest_rays += static_cast<int64_t>(sum.closest);
@@ -1655,7 +1546,6 @@ int finish_render(wr_context* c, int n, wr_stats* st, double t0_host, unsigned l
   st->verify_rays += static_cast<int64_t>(sum.verify_rays);
   st->verify_mismatches += static_cast<int64_t>(sum.verify_bad);
   st->pipelines = std::max<int64_t>(st->pipelines, n);
-  st->deferred_rays += static_cast<int64_t>(sum.deferred);
   st->bvh_width = c->fast_on ? (c->wide_now ? c->wide_now : c->fs.wide) : 0;  // the tree this render searched
   if (c->trace_log && c->fast_on) {
     unsigned long long mx[3] = {0, 0, 0};
@@ -1893,7 +1783,6 @@ static void read_knobs(wr_context& c) {
   if (const char* e = std::getenv("WR_TIE_WAVE_MAX")) c.tie_wave_max = std::max(0, std::atoi(e));
   if (const char* e = std::getenv("WR_SCAN_WAVES")) c.scan_waves = std::max(1, std::atoi(e));
   if (const char* e = std::getenv("WR_ISSUE_THREADS")) c.issue_threads = std::max(1, std::min(kMaxPipes, std::atoi(e)));
-  if (const char* e = std::getenv("WR_DEFER")) c.defer = std::atoi(e) != 0 ? 1 : 0;
   if (const char* e = std::getenv("WR_BDPT_OVERLAP")) c.bdpt_overlap = std::atoi(e) != 0;
   // k_fast_resolve's grid, given in blocks per CU
   if (const char* e = std::getenv("WR_RESOLVE_GRID")) c.resolve_blocks = std::max(0, std::atoi(e)) * c.cus;
@@ -2065,7 +1954,7 @@ static int upload_bvh(wr_context& c, const wr::Scene& s, const wr::SceneFlat& f,
   fs.diag = k.bvh_diag;
   c.fast_ok = true;
   int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fast_kernel<false, false>(wide, fs.sph, c.resolve_list), kTraceBlock,
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fast_kernel<false>(wide, fs.sph, c.resolve_list), kTraceBlock,
                                                    search_lds_bytes(fs.sdepth, wide) + (c.resolve_list ? kRlistLds : 0)) != hipSuccess ||
       per_cu <= 0)
     per_cu = 8;
@@ -2177,7 +2066,7 @@ static int trace_api(wr_context* c, const wr_ray* rays, const float* targets, in
   if (c->fast_on)
     if (int rc = c->api_t2.grow(5 * nb)) return rc;  // as ensure_t2
   QueueList ql;
-  ql.add(rq(o3, d3, n, cnt, tt, pr, tmn, tmx, occ ? dcut : nullptr), n);
+  ql.add(rq(o3, d3, n, cnt, tt, pr, occ ? dcut : nullptr, tmn, tmx), n);
   if (c->fast_on && !c->api_spill.p && max_spill_entries(c) > 0)
     if (int rc = c->api_spill.grow(max_spill_entries(c) * size_t(c->fast_blocks) * 64)) return rc;
   const TraceSlot ts{&c->ctr->fetch, c->api_t2.p, c->api_t2.n / 5, &c->ctr->hard[0], c->api_spill.p, &c->ctr->rlist};
@@ -2354,17 +2243,6 @@ static int issue_round(wr_context* c, int live, int nsteps, Fn&& fn, int np) {
 }
 }  // extern "C++"
 
-// Deferred hard rays on np pipelines: env WR_DEFER=1 only.
-static bool defer_enabled(const wr_context* c, int np) {
-  (void)np;
-  // off by default: measured slower (deferred hard rays); not
-  // built for trees with spheres (no LATE search variant with spheres)
-  return c->defer > 0 && !c->fs.sph;
-}
-
-// late-list records per group member and step parity (ties + scans) for pieces of `cap` paths
-static int late_records(int cap) { return 2 * std::max(4096, cap / 32); }
-
 static int check_bdpt(const wr_context* c, const wr_bdpt_params* prm, const float* film) {
   if (!c || !prm || !film) return fail(WR_E_ARG, "null argument");
   if (prm->width <= 0 || prm->height <= 0 || prm->iterations < 0) return fail(WR_E_ARG, "bad film size");
@@ -2430,23 +2308,11 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     for (int i = 0; i < fit; ++i)
       if (int rc = ensure_t2(c, c->pipes[i], per)) return rc;
   }
-  // Deferred hard rays: in BVH mode the extension rays a step's resolve cannot
-  // settle (near-ties, membership scans: 0.1-0.5 % of them) go to a late list
-  // instead of the step's k_fast_hard, so the step's vertex launch follows its
-  // resolve without waiting for them.  The next step's search launch settles
-  // them in extra blocks beside its search (late_hard), and its vertex launch
-  // shades their paths in extra blocks, into the same queues as its own
-  // vertices: a deferred path is one step behind, and the hard rays' latency
-  // hides under the next search instead of lengthening the chain.  A path is
-  // deferred once per pass, and each pass gets one step more (the light pass a
-  // bounce step, the camera pass extension rays at its last step).
-  // The overlapped schedule (wr_bdpt.h; WR_BDPT_OVERLAP=0: the sequential one,
-  // which the deferred hard rays need)
-  const bool overlap = c->bdpt_overlap && kMaxQueues >= 2 * kGroup && !(c->fast_on && !c->stamps && defer_enabled(c, np));
-  const bool defer = !overlap && c->fast_on && !c->stamps && defer_enabled(c, np);
-  if (defer)
-    for (int i = 0; i < fit; ++i)
-      if (int rc = ensure_late(c->pipes[i], cap, late_records(cap))) return rc;
+  // The overlapped schedule (wr_bdpt.h).  WR_BDPT_OVERLAP=0: the sequential
+  // one, the light pass and then the camera pass as the reference runs them --
+  // the schedule the overlapped one is checked against, and the one a build
+  // with fewer than 2 x kGroup queues per launch gets
+  const bool overlap = c->bdpt_overlap && kMaxQueues >= 2 * kGroup;
   float* dfilm = nullptr;
   const size_t nf = size_t(P) * 3;
   if (int rc = moments_target(c, film, M, film_on_device, nf, &dfilm)) return rc;
@@ -2491,13 +2357,12 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     Pipe* pp = nullptr;
     BdptGroup GA;
     int gn = 0, nmax = 0;
-    bool late[kSlots] = {};  // late work issued at step slot
     int fold[kGroup] = {}, nfold = 0;  // moments: the pass films complete after this group
   };
   // steps: light gen, light bounces b = 0 .. lb_n - 1, camera gen, camera bounces b = 0 .. maxlen;
   // overlapped: both gens, then bounces b = 0 .. maxlen of both passes together
-  const int lb_n = maxlen - 1 + (defer ? 1 : 0);
-  const int nsteps = overlap ? maxlen + 2 : lb_n + maxlen + 3;
+  const int lb_n = maxlen - 1;
+  const int nsteps = overlap ? maxlen + 2 : 2 * maxlen + 2;
   // The overlapped schedule: step 0 starts both subpaths of every path; step
   // b + 1 traces, per group member, the shadow / aux rays queued by the
   // vertices of bounce b - 1 (sq slot kCamSlot + b: light splats and
@@ -2536,20 +2401,19 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     for (int m = 0; m < gn; ++m) {
       const BdptBuf& B = pp.bb[m];
       const BdptBuf::Sq& Q = B.sq[slot & 1];
-      ql.add(rq(Q.o, Q.d, B.cap_sq, &pp.sc[m].sq[slot], Q.t, Q.prim, nullptr, nullptr, Q.cut),
+      ql.add(rq(Q.o, Q.d, B.cap_sq, &pp.sc[m].sq[slot], Q.t, Q.prim, Q.cut),
              std::min(A[m].n * (kVMax + 2), B.cap_sq));
-      if (light || more)
-        ql.add(rq(B.q_o[b & 1], B.q_d[b & 1], B.qs, &pp.sc[m].ext[b], B.q_t[b & 1], B.q_prim[b & 1], nullptr, nullptr,
-                  nullptr, nullptr, nullptr, 0, &pp.sc[m].ext[slot]),
-               2 * A[m].n);
+      if (light || more) {
+        RayQueue e = rq(B.q_o[b & 1], B.q_d[b & 1], B.qs, &pp.sc[m].ext[b], B.q_t[b & 1], B.q_prim[b & 1]);
+        e.count2 = &pp.sc[m].ext[slot];  // the camera pass's rays, behind the light pass's
+        ql.add(e, 2 * A[m].n);
+      }
     }
-    trace_launch(c, sm, pp.ctr, tslot(pp, slot), tm, count, ql.Q, ql.max_rays, WR_BDPT_TRACE_MODE, false, nullptr,
-                 gn);
-    LateArgs L{};
-    if (light) hipLaunchKernelGGL(k_lshade, dim3(g, gn), dim3(kShadeBlock), 0, sm, G.GA, b, L, 0);
+    trace_launch(c, sm, pp.ctr, tslot(pp, slot), tm, count, ql.Q, ql.max_rays, WR_BDPT_TRACE_MODE);
+    if (light) hipLaunchKernelGGL(k_lshade, dim3(g, gn), dim3(kShadeBlock), 0, sm, G.GA, b);
     const int nres = shade_grid(c, std::min(G.nmax * (kVMax + 2), pp.bb[0].cap_sq));
     hipLaunchKernelGGL(k_cstep, dim3(nres + (more ? g : 0), gn), dim3(kShadeBlock), 0, sm, G.GA, slot, nres,
-                       more ? 1 : 0, L, 0);
+                       more ? 1 : 0);
     tm.mark(WR_K_SHADE);
     return WR_OK;
   };
@@ -2566,53 +2430,27 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     const BdptArgs* A = G.GA.a;
     auto sq = [&](int m, int slot) {
       const BdptBuf::Sq& Q = pp.bb[m].sq[slot & 1];
-      return rq(Q.o, Q.d, pp.bb[m].cap_sq, &pp.sc[m].sq[slot], Q.t, Q.prim, nullptr, nullptr, Q.cut);
+      return rq(Q.o, Q.d, pp.bb[m].cap_sq, &pp.sc[m].sq[slot], Q.t, Q.prim, Q.cut);
     };
-    // extension rays of step `slot`; bit: the pass's deferral bit (0: not deferrable)
-    auto ext = [&](int m, int slot, int bit) {
+    auto ext = [&](int m, int slot) {  // extension rays of step `slot`
       const BdptBuf& B = pp.bb[m];
       const int q = slot & 1;
-      if (!bit) return rq(B.q_o[q], B.q_d[q], B.qs, &pp.sc[m].ext[slot], B.q_t[q], B.q_prim[q]);
-      return rq(B.q_o[q], B.q_d[q], B.qs, &pp.sc[m].ext[slot], B.q_t[q], B.q_prim[q], nullptr, nullptr, nullptr,
-                pp.late_d + 2 * m + q, pp.sc[m].late[slot], bit);
+      return rq(B.q_o[q], B.q_d[q], B.qs, &pp.sc[m].ext[slot], B.q_t[q], B.q_prim[q]);
     };
-    // the late lists of step slot - 1 (when it deferred): settled by extra
-    // blocks of step slot's search launch, shaded by extra blocks of its vertex
-    // launch, into the queues of step slot + 1
-    auto late_of = [&](int slot, LateArgs& L) -> bool {
-      if (slot < 1 || !G.late[slot - 1]) return false;
-      const int k = (slot - 1) & 1;
-      for (int m = 0; m < kGroup; ++m) {
-        L.l[m] = pp.late_h[m][k];
-        L.n[m] = pp.sc[m].late[slot - 1];
-      }
-      return true;
-    };
-    const int lg = std::max(1, std::min(shade_grid(c, G.nmax), 32));  // late-vertex blocks per member
     const int sq_max = std::min(G.nmax * (kVMax + 2), pp.bb[0].cap_sq);
     const int g = shade_grid(c, G.nmax);
     if (step == 0) {
       HIPCHK(hipMemsetAsync(pp.sc, 0, gn * sizeof(StepCounters), sm));
-      if (defer) HIPCHK(hipMemsetAsync(pp.delayed, 0, kGroup * pp.late_paths, sm));
-      for (bool& x : G.late) x = false;
       // ---------------- light pass (:67-131)
       hipLaunchKernelGGL(k_lgen, dim3(g, gn), dim3(kShadeBlock), 0, sm, G.GA);
       tm.mark(WR_K_GEN);
     } else if (step <= lb_n) {
       const int b = step - 1;
-      // deferrable up to the last regular bounce (a deferred path's next ray is
-      // traced one step late: the extra step b = maxlen - 1 traces the last ones)
-      const int bit = (defer && b <= maxlen - 2) ? 1 : 0;
-      LateArgs L{};
-      const bool lp = late_of(b, L);
       QueueList ql;
-      for (int m = 0; m < gn; ++m) ql.add(ext(m, b, bit), A[m].n);
-      trace_launch(c, sm, pp.ctr, tslot(pp, b), tm, count, ql.Q, ql.max_rays, WR_BDPT_TRACE_MODE, false,
-                   lp ? &L : nullptr, gn);
-      hipLaunchKernelGGL(k_lshade, dim3(g + (lp ? lg : 0), gn), dim3(kShadeBlock), 0, sm, G.GA, b, L,
-                         lp ? lg : 0);
+      for (int m = 0; m < gn; ++m) ql.add(ext(m, b), A[m].n);
+      trace_launch(c, sm, pp.ctr, tslot(pp, b), tm, count, ql.Q, ql.max_rays, WR_BDPT_TRACE_MODE);
+      hipLaunchKernelGGL(k_lshade, dim3(g, gn), dim3(kShadeBlock), 0, sm, G.GA, b);
       tm.mark(WR_K_SHADE);
-      G.late[b] = bit != 0;
     } else if (step == lb_n + 1) {
       // ---------------- camera pass (:133-264).  The light pass's splat rays
       // (connectToCamera) ride along with the primary rays; afterwards each
@@ -2622,23 +2460,17 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     } else {
       const int b = step - lb_n - 2;
       const int slot = kCamSlot + b;
-      const bool more = b < maxlen + (defer ? 1 : 0);  // extension rays of bounce b exist
-      const int bit = (defer && b <= maxlen - 1) ? 2 : 0;
-      LateArgs L{};
-      const bool lp = late_of(slot, L);
+      const bool more = b < maxlen;  // extension rays of bounce b exist
       QueueList ql;
       for (int m = 0; m < gn; ++m) ql.add(sq(m, slot), std::min(A[m].n * (kVMax + 2), pp.bb[m].cap_sq));
       if (more)
-        for (int m = 0; m < gn; ++m) ql.add(ext(m, slot, bit), A[m].n);
-      trace_launch(c, sm, pp.ctr, tslot(pp, slot), tm, count, ql.Q, ql.max_rays, WR_BDPT_TRACE_MODE, false,
-                   lp ? &L : nullptr, gn);
-      // resolve this step's shadow / aux rays and shade its vertices (and the
-      // previous step's deferred ones) in one launch
+        for (int m = 0; m < gn; ++m) ql.add(ext(m, slot), A[m].n);
+      trace_launch(c, sm, pp.ctr, tslot(pp, slot), tm, count, ql.Q, ql.max_rays, WR_BDPT_TRACE_MODE);
+      // resolve this step's shadow / aux rays and shade its vertices in one launch
       const int nres = shade_grid(c, sq_max);
-      hipLaunchKernelGGL(k_cstep, dim3(nres + (more ? g : 0) + (lp ? lg : 0), gn), dim3(kShadeBlock), 0, sm,
-                         G.GA, slot, nres, more ? 1 : 0, L, lp ? lg : 0);
+      hipLaunchKernelGGL(k_cstep, dim3(nres + (more ? g : 0), gn), dim3(kShadeBlock), 0, sm, G.GA, slot, nres,
+                         more ? 1 : 0);
       tm.mark(WR_K_SHADE);
-      G.late[slot] = bit != 0;
     }
     return WR_OK;
   };
@@ -2846,7 +2678,7 @@ static int render_vcm_one(wr_context* c, const wr_vcm_params* prm, float* film, 
     }
     auto sq = [&](int m, int slot) {
       const BdptBuf::Sq& Q = pp.bb[m].sq[slot & 1];
-      return rq(Q.o, Q.d, pp.bb[m].cap_sq, &pp.sc[m].sq[slot], Q.t, Q.prim, nullptr, nullptr, Q.cut);
+      return rq(Q.o, Q.d, pp.bb[m].cap_sq, &pp.sc[m].sq[slot], Q.t, Q.prim, Q.cut);
     };
     auto ext = [&](int m, int slot) {
       const BdptBuf& B = pp.bb[m];
@@ -2952,7 +2784,7 @@ static int path_radiance_one(wr_context* c, const wr_ray* rays, int64_t n64, int
     const PtBuf& T = pp.pb[0];
     const PtBuf::Sq& Q = T.sq[b & 1];
     QueueList ql;
-    ql.add(rq(Q.o, Q.d, P, &pp.sc[0].sq[b], Q.t, Q.prim, nullptr, nullptr, Q.cut), P);
+    ql.add(rq(Q.o, Q.d, P, &pp.sc[0].sq[b], Q.t, Q.prim, Q.cut), P);
     if (more) ql.add(rq(T.q_o[b & 1], T.q_d[b & 1], P, &pp.sc[0].ext[b], T.q_t[b & 1], T.q_prim[b & 1]), P);
     trace_launch(c, sm, pp.ctr, tslot(pp, b), tm, false, ql.Q, ql.max_rays, TRACE_DENSE, true);
     const int nres = shade_grid(c, P);
@@ -3047,7 +2879,7 @@ static int render_path_one(wr_context* c, const wr_path_params* prm, float* film
       for (int m = 0; m < gn; ++m) {
         const PtBuf& T = pp.pb[m];
         const PtBuf::Sq& Q = T.sq[b & 1];
-        ql.add(rq(Q.o, Q.d, P, &pp.sc[m].sq[b], Q.t, Q.prim, nullptr, nullptr, Q.cut), P);
+        ql.add(rq(Q.o, Q.d, P, &pp.sc[m].sq[b], Q.t, Q.prim, Q.cut), P);
       }
       if (more)
         for (int m = 0; m < gn; ++m) {
@@ -3094,7 +2926,6 @@ static void add_stats(wr_stats* d, const wr_stats& s) {
   d->verify_rays += s.verify_rays;
   d->verify_mismatches += s.verify_mismatches;
   d->pipelines = std::max(d->pipelines, s.pipelines);
-  d->deferred_rays += s.deferred_rays;
   d->bvh_width = std::max(d->bvh_width, s.bvh_width);
   d->work_bytes += s.work_bytes;
   d->work_paths += s.work_paths;
@@ -3209,9 +3040,6 @@ static int reserve_one(wr_context* c, int kind, int W, int H) {
   const size_t per = kGroup * (std::max(cap_sq, size_t(cap)) + 2 * size_t(cap));
   for (int i = 0; i < fit; ++i)
     if (int rc = ensure_t2(c, c->pipes[i], per)) return rc;
-  if (kind == WR_INTEGRATOR_BDPT && c->fast_on && !c->stamps && defer_enabled(c, fit))
-    for (int i = 0; i < fit; ++i)
-      if (int rc = ensure_late(c->pipes[i], cap, late_records(cap))) return rc;
   HIPCHK(hipDeviceSynchronize());
   return WR_OK;
 }
