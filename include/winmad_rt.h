@@ -362,6 +362,71 @@ typedef struct {
 int wr_film_error(wr_context* ctx, const float* film, const float* film_sq, int width, int height, int n_passes,
                   int films_on_device, float* stderr_map, wr_error_info* out);
 
+/* ---- first-hit feature films and the film denoiser (no
+ * reference counterpart).  Callers detect these entry points by their symbols
+ * (WR_API_VERSION stays 8).
+ *
+ * wr_render_features traces one ray per pixel through the pixel centre -- no
+ * RNG, so the films are deterministic -- and writes what the first hit sees.
+ * The ray is the PT primary ray (origin cam.pos, no EPS offset,
+ * d = normalize(rasterToWorld(rx, ry, 0) - cam.pos)); `layout` says which raster
+ * point a value index stands for, so that the films line up with a radiance
+ * film of that integrator:
+ *   WR_FILM_PT:   index i * width + jj  <-  raster point (jj, i)
+ *   WR_FILM_BDPT: index a * width + b   <-  raster point (a + 0.5, b + 0.5)
+ *                 (BDPT and VCM films, pre-transpose)
+ * With h the wr_hit wr_trace_closest returns for that ray:
+ *   normal = h.n, position = h.p (3 floats per pixel), depth = h.t (1 float),
+ *   albedo = min(1, diffuse + phong + specular) per channel of material
+ *            h.mat_id, (1, 1, 1) for an emitter (mat_id < 0).
+ * A miss writes zeros to every film: an all-zero normal is the "no surface"
+ * mark wr_film_denoise reads.  Each output may be NULL (not wanted); all NULL:
+ * WR_E_ARG.  films_on_device: the outputs are device pointers on the context's
+ * device (devices[0] of a wr_create_multi context, which runs the call there).
+ * Runs in the context's trace mode, ordered like a render; stats (or NULL):
+ * closest_rays and seconds.  WR_E_ARG: width or height < 1, more than 2^28
+ * pixels, a layout that is neither. */
+enum { WR_FILM_PT = 0, WR_FILM_BDPT = 1 };
+int wr_render_features(wr_context* ctx, int32_t width, int32_t height, int layout, float* normal, float* albedo,
+                       float* position, float* depth, int films_on_device, wr_stats* stats);
+
+/* wr_film_denoise: an edge-avoiding a-trous wavelet filter over the mean image
+ * of a moments render, guided by the variance of the mean per pixel (from
+ * film_sq, as wr_film_error computes it) and by the feature films.  `levels`
+ * passes of a 5 x 5 B3-spline kernel with holes, step 1, 2, 4, ...; a
+ * neighbour's weight falls with
+ *   the luminance difference, in standard errors of the pixel (sigma_l),
+ *   the angle between the normals (normal_power),
+ *   the distance of the neighbour from the pixel's tangent plane, as the sine
+ *     of the elevation angle (sigma_p),
+ *   the L1 distance of the albedos (sigma_a);
+ * surface and no-surface pixels (an all-zero normal) never mix.  DESIGN.md 11
+ * has the definition; it uses + - * / sqrt only, in a fixed order, so host
+ * films (a plain CPU loop; ctx may be NULL, no device needed) and device films
+ * (kernels on the context's device, devices[0] of a multi-device context,
+ * ordered like a render) give the same bits.
+ * film, film_sq: the two films of n_passes passes (height*width*3 floats); any
+ * of normal / position / albedo may be NULL, which sets its weight to 1.  All
+ * films live in one memory space (films_on_device).  out: height*width*3
+ * floats at the scale of `film` (a sum over n_passes), so it goes wherever
+ * `film` goes, e.g. wr_film_write_image(..., scale = 1 / n_passes).  Device
+ * films: the first call allocates two (c, v) planes and, with guides, a
+ * guide record per pixel (16 + 16 + 48 bytes per pixel) on the context, kept
+ * afterwards; a render allocates none of this.
+ * WR_E_ARG: n_passes < 2; a null film, film_sq or out; out equal to an input;
+ * width or height < 1 or more than 2^28 pixels; parameters out of range or a
+ * sigma that is not > 0; device films without a context. */
+typedef struct {
+  int32_t levels;        /* 1..8, default 5: steps 1,2,4,8,16                       */
+  int32_t normal_power;  /* w_n = max(0, Np.Nq)^(2^normal_power), 0..10, default 7   */
+  float sigma_l;         /* luminance, in standard errors; default 4                 */
+  float sigma_p;         /* plane distance, as a sine; default 0.05                  */
+  float sigma_a;         /* albedo L1 distance; default 0.1                          */
+} wr_denoise_params;     /* 20 bytes; NULL = the defaults                            */
+int wr_film_denoise(wr_context* ctx, const float* film, const float* film_sq, int width, int height, int n_passes,
+                    const float* normal, const float* position, const float* albedo, const wr_denoise_params* p,
+                    int films_on_device, float* out);
+
 /* ---- output (ImageFilm::outputImage, scene/film.cpp:39-64; BDPT transpose
  * bidirPathTracing.cpp:29-46) ---- scale -> clamp [0,1] -> pow(1/gamma) ->
  * (uchar)(x*255.0); binary PPM (RGB).  transpose != 0 swaps [i][j] <-> [j][i]

@@ -121,10 +121,11 @@ namespace {
 // the part of render() the two iteration-based integrators share: a batch is
 // rendered by plain(begin, count) or moments(begin, count), then the stop rule
 template <class Plain, class Moments>
-bool error_batch(SurfaceIntegrator& si, ErrorTarget& et, wr_context* ctx, int begin, int count, Plain plain,
-                 Moments moments) {
+bool error_batch(SurfaceIntegrator& si, ErrorTarget& et, bool denoise, wr_context* ctx, int begin, int count,
+                 Plain plain, Moments moments) {
   if (!(et.errorTarget > 0.0)) {
-    plain(begin, count);
+    if (denoise) moments(begin, count);  // the denoiser needs the squared film too
+    else plain(begin, count);
     et.iterationsDone = begin + count;
     return false;
   }
@@ -135,14 +136,41 @@ bool error_batch(SurfaceIntegrator& si, ErrorTarget& et, wr_context* ctx, int be
                    &et.errorInfo));
   return et.errorInfo.rel_stderr <= et.errorTarget;
 }
-void error_begin(SurfaceIntegrator& si, ErrorTarget& et) {
+void denoise_begin(SurfaceIntegrator& si, Denoise& dn, int passes) {
+  dn.denoised.clear();
+  if (!dn.denoise) return;
+  if (!si.checkpointPath.empty())
+    throw std::runtime_error("denoise cannot be combined with a checkpoint: the file does not carry filmSq");
+  if (passes < 2) throw std::runtime_error("denoise needs at least 2 iterations (samples): the variance of one is unknown");
+}
+void error_begin(SurfaceIntegrator& si, ErrorTarget& et, Denoise& dn, int iterations) {
   et.iterationsDone = 0;
   et.errorInfo = wr_error_info{};
+  denoise_begin(si, dn, iterations);
+  if (dn.denoise) et.filmSq.assign(si.film.size(), 0.f);
   if (!(et.errorTarget > 0.0)) return;
   if (!si.checkpointPath.empty())
     throw std::runtime_error("errorTarget cannot be combined with a checkpoint: the file does not carry filmSq");
   if (et.errorCheckEvery < 1) throw std::runtime_error("errorCheckEvery must be at least 1");
   et.filmSq.assign(si.film.size(), 0.f);
+}
+// the feature films in the film's layout, then the filter (host films: the
+// library's CPU loop); `passes` is what film / filmSq sum
+void denoise_film(SurfaceIntegrator& si, Denoise& dn, wr_context* ctx, const std::vector<float>& filmSq, int passes,
+                  int layout) {
+  if (!dn.denoise || si.stopped) return;
+  if (passes < 2) throw std::runtime_error("denoise needs at least 2 iterations (samples) in the film");
+  const size_t nf = si.film.size();
+  std::vector<float> normal(nf), position(nf), albedo(nf);
+  ok(wr_render_features(ctx, si.width, si.height, layout, normal.data(), albedo.data(), position.data(), nullptr, 0,
+                        nullptr));
+  dn.denoised.assign(nf, 0.f);
+  ok(wr_film_denoise(nullptr, si.film.data(), filmSq.data(), si.width, si.height, passes, normal.data(),
+                     position.data(), albedo.data(), &dn.denoiseParams, 0, dn.denoised.data()));
+}
+void need_denoised(const SurfaceIntegrator& si, const Denoise& dn) {
+  if (dn.denoised.size() != si.film.size() || dn.denoised.empty())
+    throw std::runtime_error("no denoised film: set denoise before render()");
 }
 void error_map(SurfaceIntegrator& si, ErrorTarget& et, const char* filename) {
   if (et.filmSq.size() != si.film.size() || et.iterationsDone < 2)
@@ -164,7 +192,7 @@ void BidirPathTracing::init(const char* filename, Parameters& para) {
 }
 
 void BidirPathTracing::render() {
-  error_begin(*this, *this);
+  error_begin(*this, *this, *this, iterations);
   batched(WR_CKPT_BDPT, iterations, seed, {double(maxPathLength), double(controlLength)}, [&](int begin, int count) {  // :25-26
     wr_bdpt_params p{};
     p.width = width;
@@ -175,10 +203,17 @@ void BidirPathTracing::render() {
     p.max_path_length = maxPathLength;
     p.seed = seed;
     p.faithful = 1;
-    return error_batch(*this, *this, ctx_, begin, count,
+    return error_batch(*this, *this, denoise, ctx_, begin, count,
                        [&](int, int) { ok(wr_render_bdpt(ctx_, &p, film.data(), 0, &stats)); },
                        [&](int, int) { ok(wr_render_bdpt_moments(ctx_, &p, film.data(), filmSq.data(), 0, &stats)); });
   }, errorTarget > 0.0 ? errorCheckEvery : 0);
+  denoise_film(*this, *this, ctx_, filmSq, iterationsDone, WR_FILM_BDPT);
+}
+
+void BidirPathTracing::outputDenoisedImage(const char* filename) {  // as outputImage
+  need_denoised(*this, *this);
+  const int n = iterationsDone > 0 ? iterationsDone : iterations;
+  ok(wr_film_write_image(denoised.data(), height, width, 1.f / n, 2.2f, height == width, filename));
 }
 
 void BidirPathTracing::outputImage(const char* filename) {
@@ -199,7 +234,7 @@ void VertexCM::init(const char* filename, Parameters& para) {
 }
 
 void VertexCM::render() {
-  error_begin(*this, *this);
+  error_begin(*this, *this, *this, iterations);
   batched(WR_CKPT_VCM, iterations, seed, {double(minPathLength), double(maxPathLength), double(baseRadiusFactor), double(radiusAlpha)}, [&](int begin, int count) {
     wr_vcm_params p{};
     p.width = width;
@@ -211,10 +246,17 @@ void VertexCM::render() {
     p.radius_factor = baseRadiusFactor;
     p.radius_alpha = radiusAlpha;
     p.seed = seed;
-    return error_batch(*this, *this, ctx_, begin, count,
+    return error_batch(*this, *this, denoise, ctx_, begin, count,
                        [&](int, int) { ok(wr_render_vcm(ctx_, &p, film.data(), 0, &stats)); },
                        [&](int, int) { ok(wr_render_vcm_moments(ctx_, &p, film.data(), filmSq.data(), 0, &stats)); });
   }, errorTarget > 0.0 ? errorCheckEvery : 0);
+  denoise_film(*this, *this, ctx_, filmSq, iterationsDone, WR_FILM_BDPT);
+}
+
+void VertexCM::outputDenoisedImage(const char* filename) {  // as outputImage
+  need_denoised(*this, *this);
+  const int n = iterationsDone > 0 ? iterationsDone : iterations;
+  ok(wr_film_write_image(denoised.data(), height, width, 1.f / n, 2.2f, height == width, filename));
 }
 
 void VertexCM::outputImage(const char* filename) {
@@ -237,6 +279,8 @@ void PathIntegrator::init(const char* filename, Parameters& para) {
 }
 
 void PathIntegrator::render() {
+  denoise_begin(*this, *this, samplesPerPixel);
+  if (denoise) filmSq.assign(film.size(), 0.f);
   batched(WR_CKPT_PT, samplesPerPixel, seed, {double(maxTracingDepth), double(samplesOfLight), double(samplesOfHemisphere)}, [&](int begin, int count) {
     wr_path_params p{};
     p.width = width;
@@ -246,12 +290,20 @@ void PathIntegrator::render() {
     p.sample_begin = begin;  // sample k of the stratification grid (surfaceIntegrator.cpp:26-32)
     p.sample_count = count;
     p.seed = seed;
-    ok(wr_render_path(ctx_, &p, film.data(), 0, &stats));
+    if (denoise) ok(wr_render_path_moments(ctx_, &p, film.data(), filmSq.data(), 0, &stats));
+    else ok(wr_render_path(ctx_, &p, film.data(), 0, &stats));
     return false;
   });
   if (stopped) return;
+  denoise_film(*this, *this, ctx_, filmSq, samplesPerPixel, WR_FILM_PT);  // of the sums, before the scale
   const float inv = 1.f / samplesPerPixel;  // film->scale(1.f / samplesPerPixel) (:45)
   for (float& v : film) v = v * inv;
+  for (float& v : denoised) v = v * inv;
+}
+
+void PathIntegrator::outputDenoisedImage(const char* filename) {  // as outputImage
+  need_denoised(*this, *this);
+  ok(wr_film_write_image(denoised.data(), height, width, 1.f, 2.2f, 0, filename));
 }
 
 void PathIntegrator::raytracing(const wr_ray* rays, int64_t n, float* rgb, int sample) {

@@ -81,12 +81,28 @@ class ErrorTarget {
   int errorCheckEvery = 4;   // iterations per batch
   int iterationsDone = 0;
   wr_error_info errorInfo{};  // of the last check (zero before the second iteration)
-  std::vector<float> filmSq;  // sum of the squared iteration films (errorTarget > 0)
+  std::vector<float> filmSq;  // sum of the squared iteration films (errorTarget > 0, or Denoise::denoise)
+};
+
+// The film denoiser (no reference counterpart; winmad_rt.h wr_film_denoise).
+// With `denoise` set, render() keeps the squared film too -- it goes through the
+// moments call even without an errorTarget -- and, once the film is complete,
+// renders the first-hit feature films in the integrator's film layout and
+// filters the film with them: `denoised` is a film like `film`, and
+// outputDenoisedImage writes it exactly as outputImage writes `film`.  Needs at
+// least 2 iterations (samples); not combined with a checkpoint (the file does
+// not carry the squared film): render() throws.
+class Denoise {
+ public:
+  bool denoise = false;
+  wr_denoise_params denoiseParams{5, 7, 4.f, 0.05f, 0.1f};
+  std::vector<float> denoised;
 };
 
 // src/surfaceIntegrator/bidirPathTracing.{h,cpp}
-class BidirPathTracing : public SurfaceIntegrator, public ErrorTarget {
+class BidirPathTracing : public SurfaceIntegrator, public ErrorTarget, public Denoise {
  public:
+  void outputDenoisedImage(const char* filename);
   // the standard-error map of the film (errorTarget > 0, >= 2 iterations), as
   // outputImage writes the film: transposed when square; .pfm keeps the floats
   void outputErrorMap(const char* filename);
@@ -99,8 +115,9 @@ class BidirPathTracing : public SurfaceIntegrator, public ErrorTarget {
 };
 
 // src/surfaceIntegrator/vertexcm.{h,cpp}
-class VertexCM : public SurfaceIntegrator, public ErrorTarget {
+class VertexCM : public SurfaceIntegrator, public ErrorTarget, public Denoise {
  public:
+  void outputDenoisedImage(const char* filename);
   void outputErrorMap(const char* filename);
   int minPathLength = 0, maxPathLength = 10;
   int iterations = 1;            // vertexcm.cpp:7
@@ -113,8 +130,10 @@ class VertexCM : public SurfaceIntegrator, public ErrorTarget {
 };
 
 // src/surfaceIntegrator/pathIntegrator.{h,cpp} + SurfaceIntegrator::render
-class PathIntegrator : public SurfaceIntegrator {
+class PathIntegrator : public SurfaceIntegrator, public Denoise {
  public:
+  void outputDenoisedImage(const char* filename);
+  std::vector<float> filmSq;  // sum of the squared sample films (denoise)
   int maxTracingDepth = 7, samplesOfLight = 8, samplesOfHemisphere = 4;
   uint32_t seed = 5489;
   void init(const char* filename, Parameters& para) override;  // pathIntegrator.cpp:3-15

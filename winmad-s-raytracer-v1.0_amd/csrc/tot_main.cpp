@@ -3,7 +3,10 @@
 //     wr_tot <scene> <out.ppm> -bpt|-vcm|-p [--params FILE] [--iterations N] [--seed S]
 //            [--device D | --gpus N | --devices D0,D1,...] [--trace bvh|reference]
 //            [--checkpoint FILE [--checkpoint-every N] [--stop-after N]] [--hw-queues N]
-//            [--target-error X [--error-every N] [--error-out map.pfm]]
+//            [--target-error X [--error-every N] [--error-out map.pfm]] [--denoise FILE]
+// --denoise FILE: also write the film filtered by the variance-guided denoiser
+// (wr_film_denoise with the first-hit feature films) to FILE, beside the normal
+// output; needs at least 2 iterations (-p: samples), not with --checkpoint.
 // --target-error X (-bpt / -vcm): render in batches of N iterations (default 4)
 // and stop at the first batch boundary where the film's relative standard error
 // (wr_film_error's rel_stderr) is at most X, or at --iterations; 0 = off.
@@ -50,13 +53,14 @@ int main(int argc, char** argv) {
                  "usage: %s <scene> <out.ppm> -bpt|-vcm|-p [--params F] [--iterations N] [--seed S] "
                  "[--device D | --gpus N | --devices D0,D1,..] [--trace bvh|reference] "
                  "[--checkpoint F [--checkpoint-every N] [--stop-after N]] [--hw-queues N] "
-                 "[--target-error X [--error-every N] [--error-out map.pfm]]\n",
+                 "[--target-error X [--error-every N] [--error-out map.pfm]] [--denoise FILE]\n",
                  argv[0]);
     return 2;
   }
   const char* params = "src/parameters.para";
   const char* checkpoint = nullptr;
   const char* error_out = nullptr;
+  const char* denoise_out = nullptr;
   double target_error = 0.0;
   bool have_target = false;
   int error_every = 4;
@@ -89,6 +93,7 @@ int main(int argc, char** argv) {
         error_every = std::atoi(v);
         if (error_every < 1) throw std::runtime_error("usage: --error-every takes a number of iterations >= 1");
       } else if (!std::strcmp(a, "--error-out")) error_out = v;
+      else if (!std::strcmp(a, "--denoise")) denoise_out = v;
       else throw std::runtime_error(std::string("unknown option ") + a);
     }
     if (have_target && !std::strcmp(argv[3], "-p"))
@@ -99,6 +104,11 @@ int main(int argc, char** argv) {
                                "(the checkpoint file does not carry the squared film)");
     if (error_out && !(target_error > 0.0))
       throw std::runtime_error("usage: --error-out needs --target-error X with X > 0");
+    if (denoise_out && checkpoint)
+      throw std::runtime_error("usage: --denoise cannot be combined with --checkpoint "
+                               "(the checkpoint file does not carry the squared film)");
+    if (denoise_out && std::strcmp(argv[3], "-p") && iterations < 2)
+      throw std::runtime_error("usage: --denoise needs --iterations of at least 2 (the variance of one is unknown)");
   } catch (const std::exception& e) {
     std::fprintf(stderr, "%s\n", e.what());
     return 2;
@@ -116,22 +126,30 @@ int main(int argc, char** argv) {
     auto t0 = std::chrono::steady_clock::now();
     std::unique_ptr<winmad::SurfaceIntegrator> integ;
     winmad::ErrorTarget* et = nullptr;
+    winmad::Denoise* dn = nullptr;
     if (!std::strcmp(argv[3], "-bpt")) {
       auto* b = new winmad::BidirPathTracing();
       b->iterations = iterations;
       b->seed = seed;
       et = b;
+      dn = b;
       integ.reset(b);
     } else if (!std::strcmp(argv[3], "-vcm")) {  // main.cpp:53-58
       auto* v = new winmad::VertexCM();
       v->iterations = iterations;
       v->seed = seed;
       et = v;
+      dn = v;
       integ.reset(v);
     } else if (!std::strcmp(argv[3], "-p")) {
       auto* p = new winmad::PathIntegrator();
       p->seed = seed;
+      dn = p;
       integ.reset(p);
+      if (denoise_out && para.SAMPLES_PER_PIXEL < 2) {
+        std::fprintf(stderr, "usage: --denoise needs at least 2 samples per pixel (the variance of one is unknown)\n");
+        return 2;
+      }
     } else {
       std::printf("error!\n");  // main.cpp:88-91
       return 1;
@@ -140,6 +158,7 @@ int main(int argc, char** argv) {
       et->errorTarget = target_error;
       et->errorCheckEvery = error_every;
     }
+    dn->denoise = denoise_out != nullptr;
     integ->device = device;
     integ->devices = devices;
     integ->traceMode = WR_TRACE_REFERENCE;
@@ -163,6 +182,11 @@ int main(int argc, char** argv) {
       return 0;
     }
     integ->outputImage(argv[2]);
+    if (denoise_out) {
+      if (auto* b = dynamic_cast<winmad::BidirPathTracing*>(integ.get())) b->outputDenoisedImage(denoise_out);
+      else if (auto* v = dynamic_cast<winmad::VertexCM*>(integ.get())) v->outputDenoisedImage(denoise_out);
+      else if (auto* p = dynamic_cast<winmad::PathIntegrator*>(integ.get())) p->outputDenoisedImage(denoise_out);
+    }
     if (et && target_error > 0.0) {
       std::printf("error %.6g after %d iterations\n", et->errorInfo.rel_stderr, et->iterationsDone);
       if (error_out) {

@@ -40,6 +40,7 @@
 #include "wr_scene.h"
 #include "wr_traverse.h"
 #include "wr_fast.h"
+#include "wr_denoise.h"
 
 using namespace wrd;
 
@@ -455,6 +456,65 @@ __global__ void __launch_bounds__(256) k_api_finish(DevScene S, const float* o3,
   }
 }
 
+// wr_render_features: one ray per pixel through the pixel
+// centre, no RNG.  Queue slot s holds value index feat_index(s): 8x8 raster
+// tiles per wave where the film's sizes allow (coherent primary rays, as the
+// BDPT camera pass), else s itself.
+__device__ __forceinline__ int feat_index(int s, int W, int H) {
+  if ((W % 8) != 0 || (H % 8) != 0) return s;
+  const int t = s >> 6, w = s & 63, tiles = W / 8;
+  return ((t / tiles) * 8 + (w >> 3)) * W + (t % tiles) * 8 + (w & 7);
+}
+// The PT primary ray (k_pt_gen: origin cam.pos, no EPS offset) through the
+// raster point the value index stands for in `layout`: PT index i W + jj is
+// (jj, i), the centre of k_pt_gen's stratification rectangle; BDPT / VCM index
+// a W + b is (a + 0.5, b + 0.5) (camera_gen_one: x = p / W, y = p % W).
+__global__ void __launch_bounds__(256) WR_NO_PK_FP32 k_feat_gen(DevScene S, int W, int H, int layout, float* o3,
+                                                                float* d3) {
+  const DCam& cam = S.cam;
+  const int n = W * H;
+  for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
+    const int l = feat_index(s, W, H);
+    const int a = l / W, b = l % W;
+    const V3 rp = layout == WR_FILM_BDPT ? v3(static_cast<float>(a) + 0.5f, static_cast<float>(b) + 0.5f, 0.f)
+                                         : v3(static_cast<float>(b), static_cast<float>(a), 0.f);
+    const V3 d = normalize(t_point(cam.r2w, rp) - cam.pos);
+    st3(o3, n, s, cam.pos);
+    st3(d3, n, s, d);
+  }
+}
+// ... after the traversal: the hit as k_api_finish rebuilds it, the albedo from
+// the material table; a miss writes zeros (an all-zero normal: "no surface")
+__global__ void __launch_bounds__(256) WR_NO_PK_FP32 k_feat_finish(DevScene S, int nmats, const float* o3,
+                                                                   const float* d3, const float* t, const int* prim,
+                                                                   int W, int H, float* normal, float* albedo,
+                                                                   float* position, float* depth) {
+  const int n = W * H;
+  for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
+    const size_t l = static_cast<size_t>(feat_index(s, W, H));
+    const int p = prim[s];
+    V3 hn = v3(0.f, 0.f, 0.f), hp = hn, al = hn;
+    float ht = 0.f;
+    if (p >= 0) {
+      const Hit x = rebuild_hit(S, p, t[s], ld3(o3, n, s), ld3(d3, n, s));
+      hn = x.n;
+      hp = x.p;
+      ht = x.t;
+      if (x.mat < 0) {
+        al = v3(1.f, 1.f, 1.f);
+      } else if (x.mat < nmats) {
+        const DMat m = S.mats[x.mat];
+        const V3 sum = m.diffuse + m.phong + m.specular;
+        al = v3(sum.x < 1.f ? sum.x : 1.f, sum.y < 1.f ? sum.y : 1.f, sum.z < 1.f ? sum.z : 1.f);
+      }
+    }
+    if (normal) normal[3 * l] = hn.x, normal[3 * l + 1] = hn.y, normal[3 * l + 2] = hn.z;
+    if (position) position[3 * l] = hp.x, position[3 * l + 1] = hp.y, position[3 * l + 2] = hp.z;
+    if (albedo) albedo[3 * l] = al.x, albedo[3 * l + 1] = al.y, albedo[3 * l + 2] = al.z;
+    if (depth) depth[l] = ht;
+  }
+}
+
 // =============================================================== BDPT, VCM, PT
 #include "wr_bdpt.h"
 #include "wr_vcm.h"
@@ -651,6 +711,10 @@ struct wr_context {
   DevBuf<double> err_acc;  // wr_film_error on device films: sum se, sum mu, max se / mu (bits), values
   DevCounters* host_ctr = nullptr;  // pinned: the pipelines' counters after a render (finish_render)
   DevBuf<char> api_tmp;  // wr_trace_closest / wr_occluded / wr_path_radiance scratch, grown on demand
+  // wr_film_denoise on device films: the two (c, v) planes the levels alternate
+  // between and the guide words (3 per pixel), allocated by the first denoise
+  DevBuf<dn::F4> dn_cv[2];
+  DevBuf<dn::F4> dn_guides;
   int grid = 2048;
   int cus = 256;
   int nmats = 0, has_sph = 0;  // entries of ds.mats; the scene has a sphere (BdptArgs)
@@ -3181,6 +3245,128 @@ int wr_film_error(wr_context* c, const float* film, const float* film_sq, int wi
   out->rel_stderr = acc[1] > 0.0 ? acc[0] / acc[1] : 0.0;
   out->max_rel_stderr = acc[2];
   out->values = static_cast<int64_t>(acc[3]);
+  return WR_OK;
+}
+
+// ---- first-hit feature films: a sibling of trace_api -- gen
+// kernel -> SoA queue -> trace_launch in the context's trace mode -> finish
+// kernel -> films.  On a multi-device context `c` is devices[0].
+int wr_render_features(wr_context* c, int32_t width, int32_t height, int layout, float* normal, float* albedo,
+                       float* position, float* depth, int films_on_device, wr_stats* st) {
+  if (!c) return fail(WR_E_ARG, "null context");
+  if (width < 1 || height < 1 || static_cast<int64_t>(width) * height > (int64_t(1) << 28))
+    return fail(WR_E_ARG, "bad film size (1 .. 2^28 pixels)");
+  if (layout != WR_FILM_PT && layout != WR_FILM_BDPT) return fail(WR_E_ARG, "layout must be WR_FILM_PT or WR_FILM_BDPT");
+  if (!normal && !albedo && !position && !depth) return fail(WR_E_ARG, "no output film");
+  DeviceGuard dg;
+  HIPCHK(hipSetDevice(c->device));
+  const double t0 = host_now();
+  const int n = width * height;
+  const size_t nb = size_t(n);
+  // scratch: the SoA queue, (t, prim), the ray count, and host films' device copies
+  const size_t bytes = nb * (4 * 8 + (films_on_device ? 0 : 4 * 10)) + 16 * 256;
+  if (int rc = api_scratch(c, bytes)) return rc;
+  char* q = c->api_tmp.p;
+  auto take = [&](size_t sz) { char* r = q; q += (sz + 255) & ~size_t(255); return r; };
+  float* o3 = reinterpret_cast<float*>(take(nb * 12));
+  float* d3 = reinterpret_cast<float*>(take(nb * 12));
+  float* tt = reinterpret_cast<float*>(take(nb * 4));
+  int* pr = reinterpret_cast<int*>(take(nb * 4));
+  int* cnt = reinterpret_cast<int*>(take(sizeof(int)));
+  float* dn_ = normal, *da = albedo, *dp = position, *dd = depth;
+  if (!films_on_device) {
+    if (normal) dn_ = reinterpret_cast<float*>(take(nb * 12));
+    if (albedo) da = reinterpret_cast<float*>(take(nb * 12));
+    if (position) dp = reinterpret_cast<float*>(take(nb * 12));
+    if (depth) dd = reinterpret_cast<float*>(take(nb * 4));
+  }
+  // after the caller's work on the legacy null stream, like a render
+  (void)hipEventRecord(c->t_null, nullptr);
+  (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
+  HIPCHK(hipMemcpyAsync(cnt, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  const int g = std::max(1, std::min(c->grid, (n + 255) / 256));
+  hipLaunchKernelGGL(k_feat_gen, dim3(g), dim3(256), 0, c->stream, c->ds, width, height, layout, o3, d3);
+  c->timing = false;
+  Timer tm(c, nullptr);
+  HIPCHK(hipMemsetAsync(c->ctr, 0, sizeof(DevCounters), c->stream));
+  if (c->fast_on)
+    if (int rc = c->api_t2.grow(5 * nb)) return rc;  // as ensure_t2
+  QueueList ql;
+  ql.add(rq(o3, d3, n, cnt, tt, pr), n);
+  if (c->fast_on && !c->api_spill.p && max_spill_entries(c) > 0)
+    if (int rc = c->api_spill.grow(max_spill_entries(c) * size_t(c->fast_blocks) * 64)) return rc;
+  const TraceSlot ts{&c->ctr->fetch, c->api_t2.p, c->api_t2.n / 5, &c->ctr->hard[0], c->api_spill.p, &c->ctr->rlist};
+  trace_launch(c, c->stream, c->ctr, ts, tm, false, ql.Q, ql.max_rays, c->api_dense ? TRACE_DENSE : TRACE_PLAIN, true);
+  hipLaunchKernelGGL(k_feat_finish, dim3(g), dim3(256), 0, c->stream, c->ds, c->nmats, o3, d3, tt, pr, width, height,
+                     dn_, da, dp, dd);
+  HIPCHK(hipGetLastError());
+  if (!films_on_device) {
+    if (normal) HIPCHK(hipMemcpyAsync(normal, dn_, nb * 12, hipMemcpyDeviceToHost, c->stream));
+    if (albedo) HIPCHK(hipMemcpyAsync(albedo, da, nb * 12, hipMemcpyDeviceToHost, c->stream));
+    if (position) HIPCHK(hipMemcpyAsync(position, dp, nb * 12, hipMemcpyDeviceToHost, c->stream));
+    if (depth) HIPCHK(hipMemcpyAsync(depth, dd, nb * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (st) {
+    *st = wr_stats{};
+    st->closest_rays = n;
+    st->seconds = host_now() - t0;
+  }
+  return WR_OK;
+}
+
+// ---- the film denoiser (wr_denoise.h)
+int wr_film_denoise(wr_context* c, const float* film, const float* film_sq, int width, int height, int n_passes,
+                    const float* normal, const float* position, const float* albedo, const wr_denoise_params* prm,
+                    int films_on_device, float* out) {
+  if (!film || !film_sq || !out) return fail(WR_E_ARG, "null film, film_sq or out");
+  if (out == film || out == film_sq || out == normal || out == position || out == albedo)
+    return fail(WR_E_ARG, "out must not be one of the inputs");
+  if (width < 1 || height < 1 || static_cast<int64_t>(width) * height > (int64_t(1) << 28))
+    return fail(WR_E_ARG, "bad film size (1 .. 2^28 pixels)");
+  if (n_passes < 2) return fail(WR_E_ARG, "the variance of the mean needs at least 2 passes");
+  const wr_denoise_params p = prm ? *prm : dn::default_params();
+  if (const char* why = dn::check_params(p)) return fail(WR_E_ARG, why);
+  if (films_on_device && !c) return fail(WR_E_ARG, "device films need a context");
+  if (!films_on_device) {  // the same filter on the CPU; needs no device
+    dn::denoise_host(film, film_sq, width, height, n_passes, normal, position, albedo, p, out);
+    return WR_OK;
+  }
+  DeviceGuard dg;
+  HIPCHK(hipSetDevice(c->device));
+  const int W = width, H = height, npix = W * H;
+  const bool guides = normal || position || albedo;
+  if (int rc = c->dn_cv[0].grow(size_t(npix))) return rc;
+  if (p.levels > 1)
+    if (int rc = c->dn_cv[1].grow(size_t(npix))) return rc;
+  if (guides)
+    if (int rc = c->dn_guides.grow(3 * size_t(npix))) return rc;
+  dn::F4* g0 = guides ? c->dn_guides.p : nullptr;
+  dn::F4* g1 = guides ? g0 + npix : nullptr;
+  dn::F4* g2 = guides ? g1 + npix : nullptr;
+  const dn::Cfg k{p.sigma_l, p.sigma_p, p.sigma_a, p.normal_power, normal != nullptr, position != nullptr,
+                  albedo != nullptr};
+  // after the caller's work on the legacy null stream, like a render
+  (void)hipEventRecord(c->t_null, nullptr);
+  (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
+  const int gp = std::max(1, std::min(c->cus * 8, (npix + 255) / 256));
+  hipLaunchKernelGGL(dn::k_dn_prepare, dim3(gp), dim3(256), 0, c->stream, film, film_sq, normal, position, albedo,
+                     npix, n_passes, c->dn_cv[0].p, g0, g1, g2);
+  const int64_t tiles = int64_t((W + dn::kTile - 1) / dn::kTile) * ((H + dn::kTile - 1) / dn::kTile);
+  const int gl = static_cast<int>(std::min<int64_t>(tiles, int64_t(1) << 20));
+  const float scale = static_cast<float>(n_passes);
+  for (int t = 0; t < p.levels; ++t) {
+    const int s = 1 << t;
+    const dn::View src{c->dn_cv[t & 1].p, g0, g1, g2, 0, 0, W};
+    dn::F4* dst = c->dn_cv[(t + 1) & 1].p;
+    const bool last = t == p.levels - 1, lds = s <= WR_DN_LDS_MAX_STEP;
+    const size_t shm = lds ? dn::lds_bytes(s) : 0;
+    auto kern = lds ? (last ? dn::k_dn_level<true, true> : dn::k_dn_level<true, false>)
+                    : (last ? dn::k_dn_level<false, true> : dn::k_dn_level<false, false>);
+    hipLaunchKernelGGL(kern, dim3(gl), dim3(dn::kBlock), shm, c->stream, src, k, W, H, s, dst, out, scale);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
   return WR_OK;
 }
 

@@ -26,8 +26,9 @@ EXPORTS = ["wr_scene_load", "wr_scene_from_desc", "wr_scene_info_get", "wr_scene
            "wr_render_bdpt", "wr_render_path", "wr_render_vcm", "wr_path_radiance", "wr_film_write_ppm",
            "wr_film_write_image", "wr_checkpoint_save", "wr_checkpoint_load", "wr_last_error", "wr_api_version",
            "wr_reserve", "wr_request_hw_queues", "wr_render_bdpt_moments", "wr_render_vcm_moments",
-           "wr_render_path_moments", "wr_film_error"]
+           "wr_render_path_moments", "wr_film_error", "wr_render_features", "wr_film_denoise"]
 CKPT_BDPT, CKPT_VCM, CKPT_PT = 1, 2, 3
+FILM_PT, FILM_BDPT = 0, 1
 
 
 class WrRay(C.Structure):
@@ -105,6 +106,15 @@ class WrErrorInfo(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class WrDenoiseParams(C.Structure):
+    """wr_denoise_params: the knobs of wr_film_denoise (the defaults are the library's)."""
+    _fields_ = [("levels", C.c_int32), ("normal_power", C.c_int32), ("sigma_l", C.c_float), ("sigma_p", C.c_float),
+                ("sigma_a", C.c_float)]
+
+    def __init__(self, levels=5, normal_power=7, sigma_l=4.0, sigma_p=0.05, sigma_a=0.1):
+        super().__init__(levels, normal_power, sigma_l, sigma_p, sigma_a)
 
 
 class WrError(RuntimeError):
@@ -201,6 +211,8 @@ def lib():
         L.wr_render_vcm_moments.argtypes = [P, C.POINTER(WrVcmParams), P, P, I, C.POINTER(WrStats)]
         L.wr_render_path_moments.argtypes = [P, C.POINTER(WrPathParams), P, P, I, C.POINTER(WrStats)]
         L.wr_film_error.argtypes = [P, P, P, I, I, I, I, P, C.POINTER(WrErrorInfo)]
+        L.wr_render_features.argtypes = [P, I, I, I, P, P, P, P, I, C.POINTER(WrStats)]
+        L.wr_film_denoise.argtypes = [P, P, P, I, I, I, P, P, P, C.POINTER(WrDenoiseParams), I, P]
         L.wr_last_error.restype = C.c_char_p
         _lib = L
     return _lib
@@ -510,6 +522,70 @@ class Context:
                                   C.c_void_p(stderr_map_ptr) if stderr_map_ptr is not None else None,
                                   C.byref(info)))
         return info
+
+    def render_features(self, width, height, layout=FILM_PT, normal_ptr=None, albedo_ptr=None, position_ptr=None,
+                        depth_ptr=None):
+        """wr_render_features: the first-hit feature films of the pixel-centre
+        rays, laid out like a radiance film of `layout` (FILM_PT / FILM_BDPT).
+        Without pointers: returns ({"normal", "albedo", "position": (height,
+        width, 3), "depth": (height, width)} float32 arrays, stats).  With
+        device pointers (any subset; None = not wanted) the films are written
+        there: returns (None, stats)."""
+        st = WrStats()
+        ptrs = (normal_ptr, albedo_ptr, position_ptr, depth_ptr)
+        if any(p is not None for p in ptrs):
+            check(lib().wr_render_features(self.h, width, height, layout,
+                                           *[C.c_void_p(p) if p is not None else None for p in ptrs], 1, C.byref(st)))
+            return None, st
+        out = {"normal": np.zeros((height, width, 3), np.float32), "albedo": np.zeros((height, width, 3), np.float32),
+               "position": np.zeros((height, width, 3), np.float32), "depth": np.zeros((height, width), np.float32)}
+        check(lib().wr_render_features(self.h, width, height, layout, out["normal"].ctypes.data_as(C.c_void_p),
+                                       out["albedo"].ctypes.data_as(C.c_void_p),
+                                       out["position"].ctypes.data_as(C.c_void_p),
+                                       out["depth"].ctypes.data_as(C.c_void_p), 0, C.byref(st)))
+        return out, st
+
+    def film_denoise(self, film_ptr, film_sq_ptr, width, height, n_passes, out_ptr, normal_ptr=None,
+                     position_ptr=None, albedo_ptr=None, **params):
+        """wr_film_denoise on device films of this context (pointers, e.g. torch
+        data_ptr()): out_ptr receives the denoised film at the scale of the
+        input film.  params: the fields of WrDenoiseParams."""
+        p = WrDenoiseParams(**params)
+        opt = [C.c_void_p(x) if x is not None else None for x in (normal_ptr, position_ptr, albedo_ptr)]
+        check(lib().wr_film_denoise(self.h, C.c_void_p(film_ptr), C.c_void_p(film_sq_ptr), width, height, n_passes,
+                                    *opt, C.byref(p), 1, C.c_void_p(out_ptr)))
+
+
+def film_denoise(film, film_sq, n_passes, normal=None, position=None, albedo=None, **params):
+    """wr_film_denoise on host films ((height, width, 3) float32: the sums of
+    n_passes passes and of their squares, and the optional guide films of
+    render_features): the variance-guided a-trous filter on the CPU -- no
+    context, no device.  Returns the denoised film at the scale of `film`.
+    params: the fields of WrDenoiseParams (levels, normal_power, sigma_l,
+    sigma_p, sigma_a)."""
+    film = np.ascontiguousarray(film, np.float32)
+    if film.ndim != 3 or film.shape[2] != 3:
+        raise ValueError(f"film must have shape (height, width, 3), got {film.shape}")
+
+    def same(a, name):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, np.float32)
+        if a.shape != film.shape:
+            raise ValueError(f"{name} must have the film's shape {film.shape}, got {a.shape}")
+        return a
+
+    film_sq = same(film_sq, "film_sq")
+    if film_sq is None:
+        raise ValueError("film_sq is required")
+    guides = [same(normal, "normal"), same(position, "position"), same(albedo, "albedo")]
+    h, w = film.shape[:2]
+    out = np.zeros_like(film)
+    p = WrDenoiseParams(**params)
+    check(lib().wr_film_denoise(None, film.ctypes.data_as(C.c_void_p), film_sq.ctypes.data_as(C.c_void_p), w, h,
+                                int(n_passes), *[g.ctypes.data_as(C.c_void_p) if g is not None else None for g in guides],
+                                C.byref(p), 0, out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 def film_error(film, film_sq, n_passes, stderr_map=False):
