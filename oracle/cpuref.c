@@ -2502,3 +2502,9 @@ void cr_kat_camera(const cr_scene* s, float x, float y, const float* w, float* o
     o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.d.x; o[4] = r.d.y; o[5] = r.d.z;
     o[6] = ras.x; o[7] = ras.y; o[8] = ras.z; o[9] = (float)cam_check(c, ras.x, ras.y);
 }
+/* Transform::tPoint(rasterToWorld, (x, y, 0)): the world point Camera::generateRay aims at (camera.cpp:37-42) */
+void cr_kat_raster_to_world(const cr_scene* s, float x, float y, float* o) {
+    init_consts();
+    v3 p = x_point(&s->cam.r2w, mk(x, y, 0));
+    o[0] = p.x; o[1] = p.y; o[2] = p.z;
+}

@@ -122,6 +122,8 @@ void cr_kat_light(const cr_scene* s, int li, const float* pos, const float* r3,
 void cr_kat_vkd(const float* pts, int n, const float* qs, int nq, float radius, int64_t* out4);
 /* out: ray origin(3) dir(3), raster(3), check */
 void cr_kat_camera(const cr_scene* s, float x, float y, const float* w, float* out10);
+/* out: the world point of raster (x, y, 0) */
+void cr_kat_raster_to_world(const cr_scene* s, float x, float y, float* out3);
 
 #ifdef __cplusplus
 }

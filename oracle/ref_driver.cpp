@@ -9,6 +9,7 @@
 //                                                KDtreeAccel.cpp:12-307)
 //   refdrv rays   SCENE PARA CORPUS.f32          Scene::intersect / occluded per ray (scene.cpp:21-81)
 //   refdrv kat    SCENE PARA N SEED              BSDF / AreaLight / sampler / camera known answers
+//   refdrv katin  SCENE PARA CASES.f32           the same answers for the inputs of a file (cmd_katin)
 //   refdrv bdpt   SCENE PARA ITERS SEED OUT.f32  BidirPathTracing::render, film pre-transpose
 //   refdrv pt     SCENE PARA SEED OUT.f32        PathIntegrator via SurfaceIntegrator::render
 //   refdrv vcm    SCENE PARA ITERS SEED OUT.f32  VertexCM::render (ref_driver_vcm.cpp)
@@ -117,31 +118,86 @@ static void cmd_rays(Scene& s, const char* corpus) {
     fclose(in);
 }
 
+// One known-answer line per call; `kat` draws the inputs from the reference's
+// RNG, `katin` reads them from a file.
+static void kat_sampler(FILE* f, const Vector3& u, Real power, const Vector3& p0, const Vector3& p1,
+                        const Vector3& p2) {
+    Real pdf = -1.f;
+    Vector3 a = sampleCosHemisphere(u, &pdf);
+    fprintf(f, "cosh"); hv3(f, u); hv3(f, a); hv(f, pdf); fprintf(f, "\n");
+    Vector3 b = samplePowerCosHemisphere(u, power, &pdf);
+    Real pp = powerCosHemispherePdf(Vector3(0, 0, 1), b, power);
+    fprintf(f, "pcosh"); hv3(f, u); hv(f, power); hv3(f, b); hv(f, pdf); hv(f, pp); fprintf(f, "\n");
+    Vector3 t = sampleTriangle(u, p0, p1, p2);
+    fprintf(f, "tri"); hv3(f, u); hv3(f, p0); hv3(f, p1); hv3(f, p2); hv3(f, t); fprintf(f, "\n");
+}
+
+static void kat_strat(FILE* f, const Vector3& u, int k) {
+    int tot = 512;
+    Vector3 v0(3.f, 4.f, 0.f), v1(4.f, 4.f, 0.f), v2(3.f, 5.f, 0.f);
+    Vector3 st = sampleRectangleStratified(u, v0, v1, v2, k, tot);
+    fprintf(f, "strat %d %d", k, tot); hv3(f, u); hv3(f, st); fprintf(f, "\n");
+}
+
+static void kat_frame(FILE* f, const Vector3& z, Real ci, Real idx) {
+    Frame fr; fr.buildFromZ(z);
+    fprintf(f, "frame"); hv3(f, z); hv3(f, fr.x); hv3(f, fr.y); hv3(f, fr.z); fprintf(f, "\n");
+    fprintf(f, "fresnel"); hv(f, ci); hv(f, idx); hv(f, fresnelDielectric(ci, idx)); fprintf(f, "\n");
+}
+
+static void kat_bsdf(FILE* f, Scene& s, int m, const Vector3& nrm, const Vector3& wi, const Vector3& wo,
+                     const Vector3& r3) {
+    Intersection inter;
+    inter.n = nrm; inter.matId = m; inter.t = 1.f; inter.inside = 0;
+    BSDF b(wi, inter, s);
+    fprintf(f, "bsdf %d", m); hv3(f, nrm); hv3(f, wi); hv3(f, wo); hv3(f, r3);
+    fprintf(f, " valid %d", (int)b.isValid());
+    if (b.isValid()) {
+        fprintf(f, " %d", (int)b.isDelta); hv(f, b.cosWi()); hv(f, b.continueProb);
+        hv(f, b.fresnelReflect); hv(f, b.componentProb.diffuseProb); hv(f, b.componentProb.glossyProb);
+        hv(f, b.componentProb.reflectProb); hv(f, b.componentProb.transProb);
+        Real cw = -7.f, dp = -7.f, rp = -7.f;
+        Color3 fv = b.f(s, wo, cw, &dp, &rp);
+        fprintf(f, " f"); hc3(f, fv); hv(f, cw); hv(f, dp); hv(f, rp);
+        fprintf(f, " pdf"); hv(f, b.pdf(s, wo, false)); hv(f, b.pdf(s, wo, true));
+        Vector3 ow(-7.f); Real spdf = -7.f, scw = -7.f; int ty = -7;
+        Color3 sv = b.sample(s, r3, ow, spdf, scw, &ty);
+        fprintf(f, " smp %d", ty); hc3(f, sv); hv3(f, ow); hv(f, spdf); hv(f, scw);
+    }
+    fprintf(f, "\n");
+}
+
+static void kat_light(FILE* f, Scene& s, int li, const Vector3& pos, const Vector3& r3, const Vector3& dr,
+                      const Vector3& pr, const Vector3& rd) {
+    AbstractLight* l = s.lights[li];
+    Vector3 dtl; Real dist = -7.f, dpdf = -7.f, epdf = -7.f, cal = -7.f;
+    Color3 il = l->illuminance(s.sceneSphere, pos, r3, dtl, dist, dpdf, &epdf, &cal);
+    fprintf(f, "illu %d", li); hv3(f, pos); hv3(f, r3); hc3(f, il); hv3(f, dtl);
+    hv(f, dist); hv(f, dpdf); hv(f, epdf); hv(f, cal); fprintf(f, "\n");
+    Vector3 ep, ed; Real emp = -7.f, dpa = -7.f, cal2 = -7.f;
+    Color3 em = l->emit(s.sceneSphere, dr, pr, ep, ed, emp, &dpa, &cal2);
+    fprintf(f, "emit %d", li); hv3(f, dr); hv3(f, pr); hc3(f, em); hv3(f, ep); hv3(f, ed);
+    hv(f, emp); hv(f, dpa); hv(f, cal2); fprintf(f, "\n");
+    Real gpa = -7.f, gep = -7.f;
+    Color3 gr = l->getRadiance(s.sceneSphere, rd, ep, &gpa, &gep);
+    fprintf(f, "rad %d", li); hv3(f, rd); hv3(f, ep); hc3(f, gr); hv(f, gpa); hv(f, gep);
+    fprintf(f, "\n");
+}
+
 static void cmd_kat(Scene& s, int n, unsigned seed) {
     RNG rng(seed);
     FILE* f = stdout;
     // samplers + frame + fresnel
     for (int i = 0; i < n; i++) {
         Vector3 u = rng.randVector3();
-        Real pdf = -1.f;
-        Vector3 a = sampleCosHemisphere(u, &pdf);
-        fprintf(f, "cosh"); hv3(f, u); hv3(f, a); hv(f, pdf); fprintf(f, "\n");
         Real power = 1.f + 200.f * rng.randFloat();
-        Vector3 b = samplePowerCosHemisphere(u, power, &pdf);
-        Real pp = powerCosHemispherePdf(Vector3(0, 0, 1), b, power);
-        fprintf(f, "pcosh"); hv3(f, u); hv(f, power); hv3(f, b); hv(f, pdf); hv(f, pp); fprintf(f, "\n");
         Vector3 p0 = rng.randVector3(), p1 = rng.randVector3(), p2 = rng.randVector3();
-        Vector3 t = sampleTriangle(u, p0, p1, p2);
-        fprintf(f, "tri"); hv3(f, u); hv3(f, p0); hv3(f, p1); hv3(f, p2); hv3(f, t); fprintf(f, "\n");
         Vector3 z = sampleUniformSphere(rng.randVector3(), NULL);
-        Frame fr; fr.buildFromZ(z);
-        fprintf(f, "frame"); hv3(f, z); hv3(f, fr.x); hv3(f, fr.y); hv3(f, fr.z); fprintf(f, "\n");
         Real ci = 2.f * rng.randFloat() - 1.f, idx = 1.f + rng.randFloat();
-        fprintf(f, "fresnel"); hv(f, ci); hv(f, idx); hv(f, fresnelDielectric(ci, idx)); fprintf(f, "\n");
-        int k = (int)(rng.randFloat() * 512), tot = 512;
-        Vector3 v0(3.f, 4.f, 0.f), v1(4.f, 4.f, 0.f), v2(3.f, 5.f, 0.f);
-        Vector3 st = sampleRectangleStratified(u, v0, v1, v2, k, tot);
-        fprintf(f, "strat %d %d", k, tot); hv3(f, u); hv3(f, st); fprintf(f, "\n");
+        int k = (int)(rng.randFloat() * 512);
+        kat_sampler(f, u, power, p0, p1, p2);
+        kat_frame(f, z, ci, idx);
+        kat_strat(f, u, k);
     }
     // BSDF per material
     for (size_t m = 1; m < s.materials.size(); m++) {
@@ -150,48 +206,19 @@ static void cmd_kat(Scene& s, int n, unsigned seed) {
             Vector3 wi = sampleUniformSphere(rng.randVector3(), NULL);
             Vector3 wo = sampleUniformSphere(rng.randVector3(), NULL);
             Vector3 r3 = rng.randVector3();
-            Intersection inter;
-            inter.n = nrm; inter.matId = (int)m; inter.t = 1.f; inter.inside = 0;
-            BSDF b(wi, inter, s);
-            fprintf(f, "bsdf %d", (int)m); hv3(f, nrm); hv3(f, wi); hv3(f, wo); hv3(f, r3);
-            fprintf(f, " valid %d", (int)b.isValid());
-            if (b.isValid()) {
-                fprintf(f, " %d", (int)b.isDelta); hv(f, b.cosWi()); hv(f, b.continueProb);
-                hv(f, b.fresnelReflect); hv(f, b.componentProb.diffuseProb); hv(f, b.componentProb.glossyProb);
-                hv(f, b.componentProb.reflectProb); hv(f, b.componentProb.transProb);
-                Real cw = -7.f, dp = -7.f, rp = -7.f;
-                Color3 fv = b.f(s, wo, cw, &dp, &rp);
-                fprintf(f, " f"); hc3(f, fv); hv(f, cw); hv(f, dp); hv(f, rp);
-                fprintf(f, " pdf"); hv(f, b.pdf(s, wo, false)); hv(f, b.pdf(s, wo, true));
-                Vector3 ow(-7.f); Real spdf = -7.f, scw = -7.f; int ty = -7;
-                Color3 sv = b.sample(s, r3, ow, spdf, scw, &ty);
-                fprintf(f, " smp %d", ty); hc3(f, sv); hv3(f, ow); hv(f, spdf); hv(f, scw);
-            }
-            fprintf(f, "\n");
+            kat_bsdf(f, s, (int)m, nrm, wi, wo, r3);
         }
     }
     // area lights
     Vector3 bl = s.kdtreeAccel.root->box.l, br = s.kdtreeAccel.root->box.r;
     for (size_t li = 0; li < s.lights.size(); li++) {
-        AbstractLight* l = s.lights[li];
         for (int i = 0; i < n; i++) {
             Vector3 u = rng.randVector3();
             Vector3 pos = bl + ((br - bl) | u);
             Vector3 r3 = rng.randVector3();
-            Vector3 dtl; Real dist = -7.f, dpdf = -7.f, epdf = -7.f, cal = -7.f;
-            Color3 il = l->illuminance(s.sceneSphere, pos, r3, dtl, dist, dpdf, &epdf, &cal);
-            fprintf(f, "illu %d", (int)li); hv3(f, pos); hv3(f, r3); hc3(f, il); hv3(f, dtl);
-            hv(f, dist); hv(f, dpdf); hv(f, epdf); hv(f, cal); fprintf(f, "\n");
             Vector3 dr = rng.randVector3(), pr = rng.randVector3();
-            Vector3 ep, ed; Real emp = -7.f, dpa = -7.f, cal2 = -7.f;
-            Color3 em = l->emit(s.sceneSphere, dr, pr, ep, ed, emp, &dpa, &cal2);
-            fprintf(f, "emit %d", (int)li); hv3(f, dr); hv3(f, pr); hc3(f, em); hv3(f, ep); hv3(f, ed);
-            hv(f, emp); hv(f, dpa); hv(f, cal2); fprintf(f, "\n");
             Vector3 rd = sampleUniformSphere(rng.randVector3(), NULL);
-            Real gpa = -7.f, gep = -7.f;
-            Color3 gr = l->getRadiance(s.sceneSphere, rd, ep, &gpa, &gep);
-            fprintf(f, "rad %d", (int)li); hv3(f, rd); hv3(f, ep); hc3(f, gr); hv(f, gpa); hv(f, gep);
-            fprintf(f, "\n");
+            kat_light(f, s, (int)li, pos, r3, dr, pr, rd);
         }
     }
     // camera
@@ -205,6 +232,30 @@ static void cmd_kat(Scene& s, int n, unsigned seed) {
         fprintf(f, "cam"); hv(f, x); hv(f, y); hv3(f, r.origin); hv3(f, r.dir); hv3(f, w); hv3(f, ras);
         fprintf(f, " %d\n", (int)c.checkRaster(ras.x, ras.y));
     }
+}
+
+// katin FILE: records of 20 floats (kind, id, 18 values); the lines are those of `kat`.
+//   kind 0  u[3] power p0[3] p1[3] p2[3] k     cosh, pcosh, tri, strat
+//   kind 1  z[3] cosI index                      frame, fresnel
+//   kind 2  n[3] wi[3] wo[3] r3[3]               bsdf of material `id`
+//   kind 3  pos[3] r3[3] dr[3] pr[3] rd[3]       illu, emit, rad of light `id`
+static void cmd_katin(Scene& s, const char* path) {
+    FILE* in = fopen(path, "rb");
+    if (!in) { fprintf(stderr, "no input file\n"); exit(2); }
+    FILE* f = stdout;
+    float r[20];
+    while (fread(r, sizeof(float), 20, in) == 20) {
+        const int kind = (int)r[0], id = (int)r[1];
+        const float* v = r + 2;
+        #define V3AT(i) Vector3(v[i], v[(i) + 1], v[(i) + 2])
+        if (kind == 0) { kat_sampler(f, V3AT(0), v[3], V3AT(4), V3AT(7), V3AT(10)); kat_strat(f, V3AT(0), (int)v[13]); }
+        else if (kind == 1) kat_frame(f, V3AT(0), v[3], v[4]);
+        else if (kind == 2 && id > 0 && id < (int)s.materials.size()) kat_bsdf(f, s, id, V3AT(0), V3AT(3), V3AT(6), V3AT(9));
+        else if (kind == 3 && id >= 0 && id < (int)s.lights.size()) kat_light(f, s, id, V3AT(0), V3AT(3), V3AT(6), V3AT(9), V3AT(12));
+        else { fprintf(stderr, "bad record kind %d id %d\n", kind, id); exit(2); }
+        #undef V3AT
+    }
+    fclose(in);
 }
 
 static void dump_film(ImageFilm* film, const char* out) {
@@ -274,12 +325,13 @@ int main(int argc, char** argv) {
     Parameters para;
     para.load_parameters(argv[3]);
     if (cwd && chdir(cwd) != 0) { perror("chdir"); }
-    if (cmd == "scene" || cmd == "rays" || cmd == "kat") {
+    if (cmd == "scene" || cmd == "rays" || cmd == "kat" || cmd == "katin") {
         Scene* s = new Scene();
         s->init(argv[2], para);
         index_objs(*s);
         if (cmd == "scene") cmd_scene(*s);
         else if (cmd == "rays") cmd_rays(*s, argv[4]);
+        else if (cmd == "katin") cmd_katin(*s, argv[4]);
         else cmd_kat(*s, atoi(argv[4]), (unsigned)strtoul(argv[5], 0, 10));
         return 0;
     }

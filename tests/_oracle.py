@@ -63,6 +63,7 @@ def lib():
         L.cr_kat_light.argtypes = [P, I, F, F, F, F, F, F]
         L.cr_kat_vkd.argtypes = [F, I, F, I, C.c_float, C.POINTER(C.c_int64)]
         L.cr_kat_camera.argtypes = [P, C.c_float, C.c_float, F, F]
+        L.cr_kat_raster_to_world.argtypes = [P, C.c_float, C.c_float, F]
         _lib = L
     return _lib
 

@@ -26,5 +26,9 @@ def spheres(W, H, mode="bdpt"):
     return path(f"spheres_{W}x{H}_{mode}.scene", scenes.spheres_scene(W, H, mode))
 
 
+def zoo(W, H, mode="bdpt", pad_materials=0):
+    return path(f"zoo_{W}x{H}_{mode}_p{pad_materials}.scene", scenes.zoo_scene(W, H, mode, pad_materials))
+
+
 def tent(W, H, mode="bdpt"):
     return path(f"tent_{W}x{H}_{mode}.scene", scenes.tent_scene(W, H, mode))

@@ -9,7 +9,9 @@ box uses the committed fixtures.
 
     python tests/golden/make_golden.py          (everything)
     python tests/golden/make_golden.py image    (the 8-bit image fixtures only)
+    python tests/golden/make_golden.py zoo      (the material-zoo fixtures only)
 """
+import gzip
 import hashlib
 import json
 import os
@@ -106,10 +108,201 @@ def image_fixtures(tmp):
             src = os.path.join(HERE, name + ".f32")
         refdrv("image", h, w, iters, tr, src, os.path.join(HERE, f"image_{name}.rgb"), cwd=tmp)
 
+# ---------------------------------------------------------------- material zoo
+# Films (scene, W, H) of scenes.zoo_scene, MT-serial, and the known answers of
+# its twelve materials: `kat` (random inputs) and `katin` (the edge inputs below).
+ZOO_KAT_N = 32
+ZOO_EDGE_CLASSES = ("sampler", "frame", "fresnel", "tangent", "below", "mirror", "otherhemi", "r3z", "tir", "normal", "light")
+ZOO_EDGE_PER_CLASS = 12
+ZOO_TIR = {5: (-1, 0.70), 6: (-1, 0.85), 7: (1, 0.60)}  # material: (sign of wi.z, largest |cos| that reflects totally)
+ZOO_POWERS = (0, 1, 3, 20, 90, 400)
+ONE_BELOW = np.float32(1.0 - 2.0 ** -24)
+
+
+def _f32(*v):
+    return np.array(v, np.float32)
+
+
+def _norm(v):
+    v = np.asarray(v, np.float32)
+    return (v / np.float32(np.sqrt(np.float32((v * v).sum())))).astype(np.float32)
+
+
+def _frame(n):
+    """frame.cpp:3-11 in float32 (inputs only: the expected values come from refdrv)."""
+    z = _norm(n)
+    tx = _f32(0, 1, 0) if abs(z[0]) > np.float32(0.99) else _f32(1, 0, 0)
+    y = _norm(np.cross(z, tx))
+    x = np.cross(y, z).astype(np.float32)
+    return x, y, z
+
+
+def _rand_dir(rng):
+    return _norm(rng.normal(size=3))
+
+
+def _local_dir(rng, n, z):
+    """A unit direction with local z component `z` in the frame of normal n."""
+    x, y, zz = _frame(n)
+    phi = rng.uniform(0, 2 * np.pi)
+    s = np.sqrt(max(0.0, 1.0 - float(z) ** 2))
+    return (x * np.float32(s * np.cos(phi)) + y * np.float32(s * np.sin(phi)) + zz * np.float32(z)).astype(np.float32)
+
+
+def _rec(label, kind, ident, *vals):
+    """One katin record: kind, id, up to 17 values, and the case's class (its
+    index in ZOO_EDGE_CLASSES) in the last float, which refdrv does not read."""
+    r = np.zeros(20, np.float32)
+    r[0], r[1], r[19] = kind, ident, ZOO_EDGE_CLASSES.index(label)
+    v = np.concatenate([np.atleast_1d(np.asarray(x, np.float32)) for x in vals])
+    r[2:2 + v.size] = v
+    return r
+
+
+def zoo_edge_normals(rng, around=8):
+    """Normals along each axis and with |n.x| on either side of 0.99 (the tangent
+    choice of frame.cpp:6), unit length up to rounding."""
+    out = []
+    for ax in range(3):
+        for sg in (1, -1):
+            v = np.zeros(3, np.float32)
+            v[ax] = sg
+            out.append(v)
+    for k in range(around):
+        x = np.float32(0.99) + np.float32((1 if k % 2 else -1) * 10.0 ** rng.uniform(-6, -2.5))
+        phi = rng.uniform(0, 2 * np.pi)
+        s = np.sqrt(1.0 - float(x) ** 2)
+        out.append(_f32((1 if k % 4 < 2 else -1) * x, s * np.cos(phi), s * np.sin(phi)))
+    return out
+
+
+def zoo_edge_cases(nmat, nlights, light_z, probs=None):
+    """The edge inputs as records (n, 20) float32.
+    probs: {record index: (pd, pg, pr)} from a first pass of the reference, for
+    the r3.z values on either side of the component thresholds (zero before)."""
+    rng = np.random.default_rng(20261019)
+    recs = []
+
+    def add(label, *a):
+        recs.append(_rec(label, *a))
+
+    # samplers: s.y in {0, 1 - 2^-24} x s.x in {0, 0.25, 0.5}, every zoo exponent
+    for sy in (np.float32(0), ONE_BELOW):
+        for sx in (0.0, 0.25, 0.5):
+            for pw in ZOO_POWERS:
+                add("sampler", 0, 0, _f32(sx, sy, rng.random()), pw, rng.random(9), int(rng.integers(0, 512)))
+    for n in zoo_edge_normals(rng, 32):
+        add("frame", 1, 0, n, rng.uniform(-1, 1), 1 + rng.random())
+    for idx in (0.75, 1.0, 1.5, 2.4):  # Fresnel at, and either side of, the critical angle and at normal incidence
+        crit = np.sqrt(max(0.0, 1.0 - min(idx, 1 / idx) ** 2))
+        cs = [1.0, -1.0, 2e-3, -2e-3]
+        if crit > 0:  # index 1 has none (and cos 0 is no valid BSDF: 0 / 0 in fresnel.cpp:24-27)
+            cs += [crit, -crit, np.nextafter(np.float32(crit), np.float32(2)), -np.nextafter(np.float32(crit), np.float32(0))]
+        for c in cs:
+            add("fresnel", 1, 0, _f32(0, 0, 1), c, idx)
+    for m in range(1, nmat):
+        for k in range(2 * ZOO_EDGE_PER_CLASS):  # wi within +-2 EPS of the tangent plane, half of them within EPS
+            n = _rand_dir(rng)
+            z = (rng.uniform(0, 0.95e-3) if k % 2 else rng.uniform(1.05e-3, 2e-3)) * rng.choice([-1, 1])
+            add("tangent", 2, m, n, _local_dir(rng, n, z), _rand_dir(rng), rng.random(3))
+        for k in range(ZOO_EDGE_PER_CLASS):  # wi below the surface
+            n = _rand_dir(rng)
+            add("below", 2, m, n, _local_dir(rng, n, -rng.uniform(0.01, 1.0)), _rand_dir(rng), rng.random(3))
+        for k in range(ZOO_EDGE_PER_CLASS):  # wo exactly the mirror direction
+            n = _rand_dir(rng)
+            wi = _local_dir(rng, n, rng.uniform(0.01, 1.0) * (1 if k % 4 else -1))
+            wo = (n * np.float32(2) * np.float32(np.dot(n, wi)) - wi).astype(np.float32)
+            add("mirror", 2, m, n, wi, wo, rng.random(3))
+        for k in range(ZOO_EDGE_PER_CLASS):  # wo in the other hemisphere
+            n = _rand_dir(rng)
+            z = rng.uniform(0.01, 1.0) * (1 if k % 2 else -1)
+            add("otherhemi", 2, m, n, _local_dir(rng, n, z), _local_dir(rng, n, -np.sign(z) * rng.uniform(0.01, 1.0)),
+                rng.random(3))
+        for base in range(2):  # r3.z at 0, 1 - 2^-24 and around pd, pd + pg, pd + pg + pr
+            n = _rand_dir(rng)
+            wi = _local_dir(rng, n, (0.8, -0.6)[base])
+            wo = _rand_dir(rng)
+            r2 = rng.random(2)
+            first = len(recs)
+            zs = [np.float32(0), ONE_BELOW]
+            pd, pg, pr = (np.float32(x) for x in (probs[first] if probs else (0, 0, 0)))
+            for t in (pd, np.float32(pd + pg), np.float32(np.float32(pd + pg) + pr)):
+                zs += [np.nextafter(t, np.float32(-1)), t, np.nextafter(t, np.float32(2))]
+            for z in zs:
+                add("r3z", 2, m, n, wi, wo, _f32(r2[0], r2[1], min(max(z, np.float32(0)), ONE_BELOW)))
+        if m in ZOO_TIR:  # total internal reflection
+            sg, cmax = ZOO_TIR[m]
+            for k in range(ZOO_EDGE_PER_CLASS):
+                n = _rand_dir(rng)
+                add("tir", 2, m, n, _local_dir(rng, n, sg * rng.uniform(0.05, cmax)), _rand_dir(rng),
+                    _f32(rng.random(), rng.random(), ONE_BELOW if k % 2 else rng.random()))
+        for n in zoo_edge_normals(rng):
+            add("normal", 2, m, n, _rand_dir(rng), _rand_dir(rng), rng.random(3))
+    # lights: shading points behind, and in the plane of, the emitter (it faces
+    # -z at z = light_z), a finite distance from it; emission at s.y = 0;
+    # radiance queries along and against the normal and in the plane
+    for li in range(nlights):
+        for k in range(16):
+            xy = rng.uniform(0.45, 1.2, 2) * rng.choice([-1, 1], 2)
+            z = light_z if k % 2 else light_z + rng.uniform(0.005, 0.8)
+            dr = _f32(rng.random(), (0.0, float(ONE_BELOW), rng.random())[k % 3], rng.random())
+            rd = (_f32(0, 0, 1), _f32(0, 0, -1), _norm(_f32(rng.normal(), rng.normal(), 0)), _rand_dir(rng))[k % 4]
+            add("light", 3, li, _f32(xy[0], xy[1], z), rng.random(3), dr, rng.random(3), rd)
+    return np.array(recs, np.float32)
+
+
+def write_gz(name, text):
+    """refdrv's text as it came, gzip-compressed (no name, no time stamp: the
+    same text gives the same file).  The zoo's answers are 0.75 MB of hex floats."""
+    with open(os.path.join(HERE, name), "wb") as f, gzip.GzipFile(filename="", mode="wb", fileobj=f, mtime=0) as z:
+        z.write(text.encode())
+
+
+def zoo_fixtures(tmp):
+    sp = scenes.write(os.path.join(tmp, "zoo24x32.scene"), scenes.zoo_scene(24, 32, "bdpt"))
+    pp = scenes.write(os.path.join(tmp, "zoo24x32.para"), scenes.params_text(24, 32))
+    write_gz("kat_zoo.txt.gz", refdrv("kat", sp, pp, ZOO_KAT_N, 777, cwd=tmp))
+    refdrv("bdpt", sp, pp, 2, 5489, os.path.join(HERE, "bdpt_zoo24x32_i2_s5489.f32"), cwd=tmp)
+    refdrv("vcm", sp, pp, 2, 3, os.path.join(HERE, "vcm_zoo24x32_i2_s3_r0.05.f32"), 0.05, cwd=tmp)
+    spt = scenes.write(os.path.join(tmp, "zoo32x24.scene"), scenes.zoo_scene(32, 24, "pt"))
+    ppt = scenes.write(os.path.join(tmp, "zoo32x24.para"), scenes.params_text(32, 24, 7, 4))
+    refdrv("pt", spt, ppt, 5489, os.path.join(HERE, "pt_zoo32x24_spp4_s5489.f32"), cwd=tmp)
+    # edge inputs: a first pass gives the reference's own component
+    # probabilities of the r3.z cases, the second pass places r3.z around them
+    dump = refdrv("scene", sp, pp, cwd=tmp).splitlines()
+    nmat = int(next(l for l in dump if l.startswith("nmat ")).split()[1])
+    lights = [l.split()[1:] for l in dump if l.startswith("light ")]
+    light_z = float.fromhex(lights[0][2])
+    cp = os.path.join(HERE, "kat_zoo_edges_in.f32")
+    recs = zoo_edge_cases(nmat, len(lights), light_z)
+    recs.tofile(cp)
+    bsdf = [l.split() for l in refdrv("katin", sp, pp, cp, cwd=tmp).splitlines() if l.startswith("bsdf ")]
+    probs, k = {}, 0
+    for i, r in enumerate(recs):
+        if r[0] != 2:
+            continue
+        t = bsdf[k]
+        k += 1
+        if ZOO_EDGE_CLASSES[int(r[19])] == "r3z" and t[15] == "1":
+            probs[i] = tuple(float.fromhex(x) for x in t[20:23])
+    recs = zoo_edge_cases(nmat, len(lights), light_z, _FirstOfRun(probs))
+    recs.tofile(cp)
+    write_gz("kat_zoo_edges.txt.gz", refdrv("katin", sp, pp, cp, cwd=tmp))
+
+
+class _FirstOfRun(dict):
+    """probs of the r3.z run that starts at a record index ((0, 0, 0) for an invalid BSDF)."""
+
+    def __getitem__(self, i):
+        return self.get(i, (0, 0, 0))
+
 
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "image":  # the image fixtures alone
         image_fixtures(tempfile.mkdtemp(prefix="wr_golden_"))
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "zoo":  # the material-zoo fixtures alone
+        zoo_fixtures(tempfile.mkdtemp(prefix="wr_golden_"))
         return
     if not os.path.exists(REFDRV):
         sys.exit("build the reference driver first: make -C oracle ref")
@@ -195,6 +388,7 @@ def main():
         extra = [] if rf is None else [rf]
         refdrv("vcm", sp, pp, it, seed, os.path.join(HERE, vcm_fixture(name, it, seed, rf)), *extra, cwd=tmp)
     image_fixtures(tmp)
+    zoo_fixtures(tmp)
     with open(os.path.join(HERE, "golden.json"), "w") as f:
         json.dump(meta, f, indent=1)
     print(json.dumps({k: v for k, v in meta.items() if "block32_mean" not in v}, indent=1))

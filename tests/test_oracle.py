@@ -275,3 +275,87 @@ def test_counter_rng_streams():
     assert len({k1, k2, k3}) == 3
     u = np.array([L.cr_stream_u32(k1, i) & 0xffffff for i in range(20000)], np.float64) / 2 ** 24
     assert abs(u.mean() - 0.5) < 0.01 and abs(u.var() - 1 / 12) < 0.005
+
+
+# ------------------------------------------------------------------ the material zoo
+def _oracle_answers(scene, k):
+    """The oracle hooks' answers for the parsed cases `k` of a kat file (tests/_kat.py layouts)."""
+    import _kat
+    e = {}
+    if "sampler" in k:
+        s = k["sampler"]
+        e["sampler"] = {"out": _kat.oracle_sampler(s["u"], s["power"], s["tri"], s["k"], s["tot"])}
+    if "frame" in k:
+        f = k["frame"]
+        e["frame"] = {"out": _kat.oracle_frame(f["z"], f["ci"], f["idx"])}
+    b = k["bsdf"]
+    out, valid = _kat.oracle_bsdf(scene, b["mat"], b["inp"])
+    e["bsdf"] = {"mat": b["mat"], "out": out, "valid": valid}
+    li = k["light"]
+    e["light"] = {"li": li["li"], "out": _kat.oracle_light(scene, li["li"], li["inp"])}
+    return e
+
+
+@pytest.mark.parametrize("name", ["kat_zoo", "kat_zoo_edges"])
+def test_kat_zoo_bit_exact(name):
+    """The twelve zoo materials (scenes.ZOO_MATERIALS: all four lobes at once,
+    coloured specular, refraction indices 0.75 / 1 / 2.4, pure Phong with
+    exponents 0 and 400, reflectance above 1, every lobe below EPS) and the two
+    luminaire triangles, on the reference's random inputs and on the edge
+    inputs of kat_zoo_edges_in.f32: every output of every case, bit for bit."""
+    import _kat
+    k = _kat.parse(name)
+    e = _oracle_answers(_oracle.Scene(_scenes.zoo(24, 32)), k)
+    assert len(k["bsdf"]["mat"]) >= 32 * 12 and set(k["bsdf"]["mat"].tolist()) == set(range(1, 13))
+    for tag in ("sampler", "frame", "bsdf", "light"):
+        _kat.same_bits(e[tag]["out"], k[tag]["out"], f"{name} {tag}")
+        assert np.all(np.isfinite(e[tag]["out"])), (name, tag)
+    assert np.array_equal(e["bsdf"]["valid"], k["bsdf"]["valid"])
+    if name == "kat_zoo":
+        c = k["cam"]
+        o = _kat.oracle_camera(_oracle.Scene(_scenes.zoo(24, 32)), c["xy"], c["w"])
+        _kat.same_bits(o[:, 3:6], c["ras"], "kat_zoo cam raster")
+        assert np.array_equal(o[:, 6].astype(np.int32), c["check"])
+    else:
+        classes = _kat.edge_classes()
+        counts = _kat.check_zoo_edge_cases(classes, e)
+        print({f"{a}/{b}": n for (a, b), n in counts.items()})
+
+
+def test_zoo_random_cases_are_not_thin():
+    """The seeded random cases tests/test_gpu_devkat.py runs on the device:
+    every oracle answer finite, at least 1 % invalid BSDFs, every sample type
+    of every mixed material in at least 5 % of its valid cases."""
+    import _kat
+    print(_kat.check_zoo_random_cases(_kat.zoo_random_cases()))
+
+
+ZOO_FILMS = {"bdpt": ("bdpt_zoo24x32_i2_s5489.f32", 24, 32), "pt": ("pt_zoo32x24_spp4_s5489.f32", 32, 24),
+             "vcm": ("vcm_zoo24x32_i2_s3_r0.05.f32", 24, 32)}
+
+
+def _zoo_film(kind, pad, mode):
+    fx, W, H = ZOO_FILMS[kind]
+    if kind == "bdpt":
+        return _oracle.Scene(_scenes.zoo(W, H, "bdpt", pad)).bdpt(W, H, 2, 5489, mode=mode)
+    if kind == "pt":
+        return _oracle.Scene(_scenes.zoo(W, H, "pt", pad)).pt(W, H, 4, 7, 5489, mode=mode)
+    return _oracle.Scene(_scenes.zoo(W, H, "bdpt", pad)).vcm(W, H, 2, 3, mode=mode, radius_factor=0.05)
+
+
+@pytest.mark.parametrize("kind", list(ZOO_FILMS))
+def test_zoo_films_mt_serial_bit_exact(kind):
+    """Whole BDPT / PT / VCM renders of the zoo against the reference's own films;
+    the scene padded to 43 materials (objects shaded through ids up to 42)
+    gives the same film."""
+    fx, W, H = ZOO_FILMS[kind]
+    ref = np.fromfile(os.path.join(GOLD, fx), np.float32).reshape(H, W, 3)
+    film, st = _zoo_film(kind, 0, 0)
+    assert np.all(np.isfinite(ref)) and ref.max() > 0
+    assert np.array_equal(film.view(np.uint32), ref.view(np.uint32))
+    assert st.closest_rays > 1000 and st.shadow_rays > 1000
+    if kind == "vcm":
+        assert st.vm_merged > 1000
+    padded, pst = _zoo_film(kind, 30, 0)
+    assert np.array_equal(padded.view(np.uint32), ref.view(np.uint32))
+    assert (pst.closest_rays, pst.shadow_rays, pst.vm_merged) == (st.closest_rays, st.shadow_rays, st.vm_merged)

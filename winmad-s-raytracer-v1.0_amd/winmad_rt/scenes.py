@@ -12,6 +12,8 @@ Writers:
   torus_scene(W, H)     -- torus.scene (C1/C2), mirror object kept (file absent
                            in the reference => 0 triangles, as there)
   cbox_scene(W, H)      -- Cornell box + test_out_dragon.obj (C3)
+  spheres_scene / tent_scene / zoo_scene -- Cornell walls with spheres: glass and
+                           mirror, a tent luminaire, and the material zoo (tests)
   synth_torus_obj(path) -- the 1M-triangle torus of C4/C5
 """
 import math
@@ -159,6 +161,67 @@ def tent_scene(width, height, mode="bdpt", assets=ASSETS):
     out += _obj(a("cbox_redwall.obj"), 3)
     out += _sphere(("0.1", "0.2", "-0.8"), "0.35", 4)
     out += _area(a("tent_luminaire.obj"), "12")
+    out += "</scene>\n"
+    return out
+
+
+# The material zoo: every BSDF branch the five materials of the other scenes
+# leave out.  (diffuse, phong, specular, phongExp, refracIndex) per material id.
+# Phong exponents are integers: glossy_rho takes powf of a lobe cosine that may
+# be negative, and powf(negative, fraction) is NaN in the reference's formula.
+ZOO_MATERIALS = [
+    dict(d=("0.803922", "0.803922", "0.803922"), e=1),                    # 1 white diffuse (ceiling)
+    dict(d=("0.156863", "0.803922", "0.172549"), e=1),                    # 2 green wall
+    dict(d=("0.803922", "0.152941", "0.152941"), e=1),                    # 3 red wall
+    dict(d=("0.4", "0.4", "0.4"), g=("0.3", "0.3", "0.3"), e=3),          # 4 diffuse + Phong 3 (back wall)
+    dict(d=("0.3", "0.2", "0.1"), g=("0.2", "0.2", "0.2"), s=("0.3", "0.3", "0.3"), e=20, n="1.5"),  # 5 all four lobes
+    dict(s=("0.9", "0.6", "0.2"), n="2.4"),                               # 6 coloured specular, dense glass
+    dict(s=("1", "1", "1"), n="0.75"),                                    # 7 refraction index below 1
+    dict(s=("1", "1", "1"), n="1"),                                       # 8 refraction index 1 (Fresnel 0)
+    dict(g=("0.6", "0.6", "0.6"), e=400),                                 # 9 pure Phong, exponent 400
+    dict(g=("0.5", "0.4", "0.3"), e=0),                                   # 10 pure Phong, exponent 0, coloured
+    dict(d=("0.7", "0.7", "0.7"), g=("0.5", "0.5", "0.5"), e=90),         # 11 reflectance 1.2: continueProb clamps (floor)
+    dict(d=("0.0005", "0.0005", "0.0005")),                               # 12 every lobe below EPS
+]
+ZOO_SPHERES = [(("-0.65", "0.45", "-1.0"), "0.28", 5), (("0.0", "0.55", "-1.0"), "0.28", 6),
+               (("0.65", "0.45", "-1.0"), "0.28", 7), (("-0.65", "-0.35", "-1.04"), "0.24", 8),
+               (("0.0", "-0.4", "-1.04"), "0.24", 9), (("0.65", "-0.35", "-1.04"), "0.24", 10),
+               (("0.0", "0.1", "0.1"), "0.2", 12)]
+
+
+def zoo_material_id(matid, pad_materials=0):
+    """The id an object of zoo material `matid` carries in the padded scene:
+    its highest-numbered copy (the material itself without padding)."""
+    n = len(ZOO_MATERIALS)
+    copies = [n + 1 + k for k in range(pad_materials) if k % n == matid - 1]
+    return copies[-1] if copies else matid
+
+
+def zoo_scene(width, height, mode="bdpt", pad_materials=0, assets=ASSETS):
+    """Cornell-box walls and luminaire plus seven spheres carrying ZOO_MATERIALS.
+    pad_materials appends that many copies of materials 1, 2, ... (cyclically);
+    every object then refers to the last copy of its material, so the same
+    picture is shaded from material ids up to 12 + pad_materials (30 copies:
+    43 materials, more than the vertex kernels keep in LDS, ten of the twelve
+    used through ids above 32)."""
+    xres, yres = (width, height) if mode == "pt" else (height, width)
+    a = lambda f: os.path.join(assets, f)
+    mid = lambda m: zoo_material_id(m, pad_materials)
+    out = "<scene>\n"
+    out += _camera(("-0.0439815", "-4.12529", "0.222539"),
+                   ("0.00688625", "0.998505", "-0.0542161"),
+                   ("3.73896e-4", "0.0542148", "0.998529"), xres, yres, "45")
+    out += _mat()
+    for k in range(len(ZOO_MATERIALS) + pad_materials):
+        out += _mat(**ZOO_MATERIALS[k % len(ZOO_MATERIALS)])
+    out += _obj(a("cbox_floor.obj"), mid(11))
+    out += _obj(a("cbox_back.obj"), mid(4))
+    out += _obj(a("cbox_ceiling.obj"), mid(1))
+    out += _obj(a("cbox_greenwall.obj"), mid(2))
+    out += _obj(a("cbox_redwall.obj"), mid(3))
+    for c, r, m in ZOO_SPHERES:
+        out += _sphere(c, r, mid(m))
+    out += _area(a("cbox_luminaire.obj"), "25.03329895614464")
     out += "</scene>\n"
     return out
 
