@@ -427,6 +427,48 @@ int wr_film_denoise(wr_context* ctx, const float* film, const float* film_sq, in
                     const float* normal, const float* position, const float* albedo, const wr_denoise_params* p,
                     int films_on_device, float* out);
 
+/* ---- ray batches that already live on the GPU (no reference
+ * counterpart).  Callers detect these entry points by their symbols
+ * (WR_API_VERSION stays 8).
+ *
+ * The three _dev calls are wr_trace_closest, wr_occluded and wr_path_radiance
+ * for arrays in device memory: the same kernels read the caller's rays where
+ * they lie and write the caller's outputs directly, so the answers are the host
+ * calls' bit for bit and nothing crosses to the host.  Trace mode, the ray
+ * limits (2^28; 2^26 for radiance), n == 0 and WR_E_SCENE are as in the host
+ * calls.
+ *   Ownership: the caller owns every array and keeps it alive and unchanged
+ *     until the call returns.  Every pointer is device memory on the context's
+ *     device (devices[0] of a wr_create_multi context, which runs the call
+ *     there and does not share it out).  Records need only 4-byte alignment
+ *     (`occluded`: any), so a slice rays + 1 or hits + 1 is fine.
+ *   Streams: the call is ordered after all work submitted before it on the
+ *     legacy null stream (torch's default stream); work on another caller
+ *     stream that writes an input or output must be synchronized by the caller
+ *     first.  The call returns when the outputs are written.
+ *   WR_E_ARG: a null pointer with n > 0; n < 0 or over the limit; max_depth out
+ *     of range; an output range that overlaps an input range or another output;
+ *     a pointer that is not device memory of the context's device (host and
+ *     pinned host memory belong to the host calls).
+ * wr_path_radiance_dev accumulates (+=) the radiance of each ray into rgb (n*3
+ * floats), like a device film: zero it for a plain radiance.  rgb_sq (or NULL):
+ * n*3 floats that receive += the square of this call's radiance, per value, so
+ * that one call per sample index builds the (film, film_sq) pair of an n x 1
+ * film that wr_film_error (n_passes = calls) and wr_film_denoise read.  Ray k
+ * draws from stream (seed, sample, 2, k) as in wr_path_radiance.  The first
+ * call with rgb_sq allocates a pass film on the context, kept afterwards. */
+int wr_trace_closest_dev(wr_context* ctx, const wr_ray* rays, int64_t n, wr_hit* hits);
+int wr_occluded_dev(wr_context* ctx, const wr_ray* rays, const float* targets, int64_t n, uint8_t* occluded);
+int wr_path_radiance_dev(wr_context* ctx, const wr_ray* rays, int64_t n, int32_t max_depth, uint32_t seed,
+                         int32_t sample, float* rgb, float* rgb_sq, wr_stats* stats);
+/* The ray wr_render_features traces for every value index of a width x height
+ * film in `layout` (origin cam.pos, d = normalize(rasterToWorld(..) - cam.pos),
+ * tmin 0, tmax 1e7), as wr_ray records: rays[index].  rays_on_device as
+ * films_on_device of wr_render_features; ordered like a render.  A caller
+ * perturbs them on the device (a thin lens, a panorama) and hands them to the
+ * _dev calls.  WR_E_ARG: as wr_render_features; null rays. */
+int wr_camera_rays(wr_context* ctx, int32_t width, int32_t height, int layout, wr_ray* rays, int rays_on_device);
+
 /* ---- output (ImageFilm::outputImage, scene/film.cpp:39-64; BDPT transpose
  * bidirPathTracing.cpp:29-46) ---- scale -> clamp [0,1] -> pow(1/gamma) ->
  * (uchar)(x*255.0); binary PPM (RGB).  transpose != 0 swaps [i][j] <-> [j][i]

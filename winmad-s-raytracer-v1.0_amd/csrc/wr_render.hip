@@ -469,18 +469,40 @@ __device__ __forceinline__ int feat_index(int s, int W, int H) {
 // raster point the value index stands for in `layout`: PT index i W + jj is
 // (jj, i), the centre of k_pt_gen's stratification rectangle; BDPT / VCM index
 // a W + b is (a + 0.5, b + 0.5) (camera_gen_one: x = p / W, y = p % W).
+// The direction of that ray for value index l: the one arithmetic of
+// k_feat_gen and k_camera_rays (wr_camera_rays), so the two cannot drift.
+__device__ __forceinline__ WR_NO_PK_FP32 V3 feat_ray_dir(const DCam& cam, int l, int W, int layout) {
+  const int a = l / W, b = l % W;
+  const V3 rp = layout == WR_FILM_BDPT ? v3(static_cast<float>(a) + 0.5f, static_cast<float>(b) + 0.5f, 0.f)
+                                       : v3(static_cast<float>(b), static_cast<float>(a), 0.f);
+  return normalize(t_point(cam.r2w, rp) - cam.pos);
+}
 __global__ void __launch_bounds__(256) WR_NO_PK_FP32 k_feat_gen(DevScene S, int W, int H, int layout, float* o3,
                                                                 float* d3) {
   const DCam& cam = S.cam;
   const int n = W * H;
   for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
-    const int l = feat_index(s, W, H);
-    const int a = l / W, b = l % W;
-    const V3 rp = layout == WR_FILM_BDPT ? v3(static_cast<float>(a) + 0.5f, static_cast<float>(b) + 0.5f, 0.f)
-                                         : v3(static_cast<float>(b), static_cast<float>(a), 0.f);
-    const V3 d = normalize(t_point(cam.r2w, rp) - cam.pos);
+    const V3 d = feat_ray_dir(cam, feat_index(s, W, H), W, layout);
     st3(o3, n, s, cam.pos);
     st3(d3, n, s, d);
+  }
+}
+// wr_camera_rays: the same rays as wr_ray records (tmin 0, tmax INF as the
+// reference's Ray), each at its value index -- feat_index is k_feat_gen's queue
+// order, not an output order.  wr_ray has 4-byte members only, so the store
+// assumes no more alignment than a caller's slice has.
+__global__ void __launch_bounds__(256) WR_NO_PK_FP32 k_camera_rays(DevScene S, int W, int H, int layout,
+                                                                   wr_ray* rays) {
+  const DCam& cam = S.cam;
+  const int n = W * H;
+  for (int l = blockIdx.x * blockDim.x + threadIdx.x; l < n; l += gridDim.x * blockDim.x) {
+    const V3 d = feat_ray_dir(cam, l, W, layout);
+    wr_ray r;
+    r.o[0] = cam.pos.x; r.o[1] = cam.pos.y; r.o[2] = cam.pos.z;
+    r.d[0] = d.x; r.d[1] = d.y; r.d[2] = d.z;
+    r.tmin = 0.f;
+    r.tmax = WR_INF;
+    rays[l] = r;
   }
 }
 // ... after the traversal: the hit as k_api_finish rebuilds it, the albedo from
@@ -2093,34 +2115,85 @@ void wr_destroy(wr_context* c) {
 // between API calls: every call ends with a stream synchronize)
 static int api_scratch(wr_context* c, size_t bytes) { return c->api_tmp.grow(bytes); }
 
+// ---- device-resident ray batches (wr_*_dev, wr_camera_rays).
+// A caller's mistake must not become a GPU fault: every pointer of a _dev call
+// is looked up (its first and last byte) and has to be device memory of the
+// context's device.  A failed query leaves HIP's sticky error set: cleared here.
+static int check_dev_range(const wr_context* c, const void* p, size_t bytes, const char* what,
+                           const char* host_call) {
+  const char* b = static_cast<const char*>(p);
+  for (const char* q : {b, b + (bytes ? bytes - 1 : 0)}) {
+    hipPointerAttribute_t at{};
+    const hipError_t e = hipPointerGetAttributes(&at, q);
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (e != hipSuccess || at.type != hipMemoryTypeDevice)
+      return fail(WR_E_ARG, std::string(what) + " is not device memory (host or pinned host memory goes to " +
+                                host_call + ")");
+    if (at.device != c->device)
+      return fail(WR_E_ARG, std::string(what) + " lives on device " + std::to_string(at.device) +
+                                ", the context on device " + std::to_string(c->device));
+  }
+  return WR_OK;
+}
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return a && b && x < y + nb && y < x + na;
+}
+
+// wr_trace_closest / wr_occluded and their _dev forms: prep kernel -> SoA queue
+// -> trace_launch -> finish kernel.  Host arrays (on_device false) are staged
+// in the context's scratch and the answers copied back; device arrays are read
+// and written where they lie, after the caller's work on the legacy null
+// stream, and the scratch holds only the queue, (t, prim), cut and the counter.
 static int trace_api(wr_context* c, const wr_ray* rays, const float* targets, int64_t n64, wr_hit* hits,
-                     uint8_t* occ) {
+                     uint8_t* occ, bool on_device = false) {
   if (!c || (!rays && n64) || n64 < 0) return fail(WR_E_ARG, "bad argument");
   if (n64 == 0) return WR_OK;
   if (n64 > (1 << 28)) return fail(WR_E_ARG, "at most 2^28 rays per call");
   const int n = static_cast<int>(n64);
+  const size_t nb = size_t(n);
+  if (on_device) {
+    const char* host_call = occ ? "wr_occluded" : "wr_trace_closest";
+    if (int rc = check_dev_range(c, rays, nb * sizeof(wr_ray), "rays", host_call)) return rc;
+    if (occ) {
+      if (int rc = check_dev_range(c, targets, nb * 12, "targets", host_call)) return rc;
+      if (int rc = check_dev_range(c, occ, nb, "occluded", host_call)) return rc;
+      if (ranges_overlap(occ, nb, rays, nb * sizeof(wr_ray)) || ranges_overlap(occ, nb, targets, nb * 12))
+        return fail(WR_E_ARG, "occluded overlaps an input");
+    } else {
+      if (int rc = check_dev_range(c, hits, nb * sizeof(wr_hit), "hits", host_call)) return rc;
+      if (ranges_overlap(hits, nb * sizeof(wr_hit), rays, nb * sizeof(wr_ray)))
+        return fail(WR_E_ARG, "hits overlaps rays");
+    }
+  }
   HIPCHK(hipSetDevice(c->device));
   // one scratch block: rays, SoA queue, results, counters (kept on the
   // context: no allocation per call, nothing to free on an error return)
-  const size_t nb = size_t(n);
-  const size_t bytes = nb * (sizeof(wr_ray) + 4 * 14 + sizeof(wr_hit) + 1) + 16 * 256;
+  const size_t bytes = nb * ((on_device ? 0 : sizeof(wr_ray) + 12 + sizeof(wr_hit) + 1) + 4 * 11) + 16 * 256;
   if (int rc = api_scratch(c, bytes)) return rc;
   char* q = c->api_tmp.p;
   auto take = [&](size_t sz) { char* r = q; q += (sz + 255) & ~size_t(255); return r; };
-  wr_ray* dr = reinterpret_cast<wr_ray*>(take(nb * sizeof(wr_ray)));
+  const wr_ray* dr = on_device ? rays : reinterpret_cast<wr_ray*>(take(nb * sizeof(wr_ray)));
   float* o3 = reinterpret_cast<float*>(take(nb * 12));
   float* d3 = reinterpret_cast<float*>(take(nb * 12));
   float* tmn = reinterpret_cast<float*>(take(nb * 4));
   float* tmx = reinterpret_cast<float*>(take(nb * 4));
   float* tt = reinterpret_cast<float*>(take(nb * 4));
   int* pr = reinterpret_cast<int*>(take(nb * 4));
-  float* dtg = reinterpret_cast<float*>(take(nb * 12));
+  const float* dtg = on_device ? targets : reinterpret_cast<float*>(take(nb * 12));
   float* dcut = reinterpret_cast<float*>(take(nb * 4));
-  wr_hit* dh = reinterpret_cast<wr_hit*>(take(nb * sizeof(wr_hit)));
-  uint8_t* dox = reinterpret_cast<uint8_t*>(take(nb));
+  wr_hit* dh = on_device ? hits : reinterpret_cast<wr_hit*>(take(nb * sizeof(wr_hit)));
+  uint8_t* dox = on_device ? occ : reinterpret_cast<uint8_t*>(take(nb));
   int* cnt = reinterpret_cast<int*>(take(sizeof(int)));
-  HIPCHK(hipMemcpyAsync(dr, rays, nb * sizeof(wr_ray), hipMemcpyHostToDevice, c->stream));
-  if (occ) HIPCHK(hipMemcpyAsync(dtg, targets, nb * 12, hipMemcpyHostToDevice, c->stream));
+  if (on_device) {
+    // after the caller's work on the legacy null stream, like a render
+    (void)hipEventRecord(c->t_null, nullptr);
+    (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
+  } else {
+    HIPCHK(hipMemcpyAsync(const_cast<wr_ray*>(dr), rays, nb * sizeof(wr_ray), hipMemcpyHostToDevice, c->stream));
+    if (occ)
+      HIPCHK(hipMemcpyAsync(const_cast<float*>(dtg), targets, nb * 12, hipMemcpyHostToDevice, c->stream));
+  }
   HIPCHK(hipMemcpyAsync(cnt, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
   const int g = std::max(1, std::min(c->grid, (n + 255) / 256));
   hipLaunchKernelGGL(k_api_prep, dim3(g), dim3(256), 0, c->stream, dr, n, occ ? 1 : 0, o3, d3, tmn, tmx, dtg, dcut);
@@ -2139,8 +2212,10 @@ static int trace_api(wr_context* c, const wr_ray* rays, const float* targets, in
   hipLaunchKernelGGL(k_api_finish, dim3(g), dim3(256), 0, c->stream, c->ds, o3, d3, tt, pr, dtg, n, dh,
                      occ ? dox : nullptr);
   HIPCHK(hipGetLastError());
-  if (occ) HIPCHK(hipMemcpyAsync(occ, dox, nb, hipMemcpyDeviceToHost, c->stream));
-  else HIPCHK(hipMemcpyAsync(hits, dh, nb * sizeof(wr_hit), hipMemcpyDeviceToHost, c->stream));
+  if (!on_device) {
+    if (occ) HIPCHK(hipMemcpyAsync(occ, dox, nb, hipMemcpyDeviceToHost, c->stream));
+    else HIPCHK(hipMemcpyAsync(hits, dh, nb * sizeof(wr_hit), hipMemcpyDeviceToHost, c->stream));
+  }
   HIPCHK(hipStreamSynchronize(c->stream));
   return WR_OK;
 }
@@ -2194,6 +2269,22 @@ int wr_occluded(wr_context* c, const wr_ray* rays, const float* targets, int64_t
   if (!c || (!rays && n) || n < 0) return fail(WR_E_ARG, "bad argument");
   DeviceGuard dg;
   return trace_multi(c, rays, targets, n, nullptr, occluded);
+}
+
+// Device arrays on the context's device (devices[0] of a multi-device context,
+// not shared out, as wr_render_features).
+int wr_trace_closest_dev(wr_context* c, const wr_ray* rays, int64_t n, wr_hit* hits) {
+  if (!c) return fail(WR_E_ARG, "null context");
+  if ((!rays || !hits) && n) return fail(WR_E_ARG, "null rays / hits");
+  DeviceGuard dg;
+  return trace_api(c, rays, nullptr, n, hits, nullptr, true);
+}
+
+int wr_occluded_dev(wr_context* c, const wr_ray* rays, const float* targets, int64_t n, uint8_t* occluded) {
+  if (!c) return fail(WR_E_ARG, "null context");
+  if ((!rays || !targets || !occluded) && n) return fail(WR_E_ARG, "null rays / targets / output");
+  DeviceGuard dg;
+  return trace_api(c, rays, targets, n, nullptr, occluded, true);
 }
 
 static int film_target(wr_context* c, float* film, int film_on_device, size_t nfloat, float** dev) {
@@ -2806,22 +2897,43 @@ static int check_radiance(const wr_context* c, const wr_ray* rays, int64_t n64, 
   if (c->ds.nlights <= 0) return fail(WR_E_SCENE, "path tracing needs at least one area light");
   return WR_OK;
 }
+// on_device (wr_path_radiance_dev): rays, rgb and rgb_sq are device arrays, read
+// and accumulated into (+=) where they lie.  With rgb_sq the sample renders
+// into pipeline 0's pass film, which k_film_fold adds to rgb and, squared, to
+// rgb_sq, as a PT moments render does per sample.
 static int path_radiance_one(wr_context* c, const wr_ray* rays, int64_t n64, int32_t max_depth, uint32_t seed,
-                             int32_t sample, float* rgb, wr_stats* st) {
+                             int32_t sample, float* rgb, wr_stats* st, bool on_device = false,
+                             float* rgb_sq = nullptr) {
   if (n64 == 0) return WR_OK;
+  const int P = static_cast<int>(n64);
+  const size_t nf = size_t(P) * 3;
+  if (on_device) {
+    const size_t rb = size_t(P) * sizeof(wr_ray), fb = nf * sizeof(float);
+    if (int rc = check_dev_range(c, rays, rb, "rays", "wr_path_radiance")) return rc;
+    if (int rc = check_dev_range(c, rgb, fb, "rgb", "wr_path_radiance")) return rc;
+    if (rgb_sq)
+      if (int rc = check_dev_range(c, rgb_sq, fb, "rgb_sq", "wr_path_radiance")) return rc;
+    if (ranges_overlap(rgb, fb, rays, rb) || ranges_overlap(rgb_sq, fb, rays, rb) || ranges_overlap(rgb, fb, rgb_sq, fb))
+      return fail(WR_E_ARG, "rgb / rgb_sq overlap an input or each other");
+  }
   HIPCHK(hipSetDevice(c->device));
   const double t0 = host_now();
-  const int P = static_cast<int>(n64);
   if (pipelines_that_fit(c, 2, P, 1, 1) < 1) return WR_E_HIP;
   if (int rc = ensure_t2(c, c->pipes[0], 2 * size_t(P))) return rc;
   Pipe& pp = c->pipes[0];  // the context stream
-  const size_t nf = size_t(P) * 3;
-  std::memset(rgb, 0, nf * sizeof(float));
-  float* dfilm = nullptr;
-  if (int rc = film_target(c, rgb, 0, nf, &dfilm)) return rc;
-  if (int rc = api_scratch(c, size_t(P) * sizeof(wr_ray))) return rc;
-  wr_ray* drays = reinterpret_cast<wr_ray*>(c->api_tmp.p);
-  HIPCHK(hipMemcpyAsync(drays, rays, size_t(P) * sizeof(wr_ray), hipMemcpyHostToDevice, pp.stream));
+  float* dfilm = rgb;
+  const wr_ray* drays = rays;
+  if (!on_device) {
+    std::memset(rgb, 0, nf * sizeof(float));
+    if (int rc = film_target(c, rgb, 0, nf, &dfilm)) return rc;
+    if (int rc = api_scratch(c, size_t(P) * sizeof(wr_ray))) return rc;
+    wr_ray* staged = reinterpret_cast<wr_ray*>(c->api_tmp.p);
+    HIPCHK(hipMemcpyAsync(staged, rays, size_t(P) * sizeof(wr_ray), hipMemcpyHostToDevice, pp.stream));
+    drays = staged;
+  } else if (rgb_sq) {
+    if (int rc = ensure_moments(c, 1, nf)) return rc;
+    c->mom_dirty = true;  // until the call has finished
+  }
   begin_render(c, 1, 0);
   PtGroup GA;
   PtArgs& A = GA.a[0];
@@ -2829,7 +2941,7 @@ static int path_radiance_one(wr_context* c, const wr_ray* rays, int64_t n64, int
   A.T = pp.pb[0];
   A.ctr = pp.ctr;
   A.sc = pp.sc;
-  A.film = dfilm;
+  A.film = rgb_sq ? pp.mom[0].p : dfilm;
   A.W = P;
   A.H = 1;
   A.P = P;
@@ -2856,8 +2968,13 @@ static int path_radiance_one(wr_context* c, const wr_ray* rays, int64_t n64, int
                        more ? 1 : 0);
     if (!more) break;
   }
+  if (rgb_sq) fold_launch(c, pp, 0, dfilm, rgb_sq, nf);
   HIPCHK(hipGetLastError());
   if (int rc = finish_render(c, 1, st, t0)) return rc;
+  if (on_device) {
+    if (rgb_sq) c->mom_dirty = false;
+    return WR_OK;
+  }
   return film_return(c, rgb, 0, nf);
 }
 
@@ -3375,6 +3492,43 @@ int wr_path_radiance(wr_context* c, const wr_ray* rays, int64_t n64, int32_t max
   if (int rc = check_radiance(c, rays, n64, max_depth, rgb)) return rc;
   DeviceGuard dg;
   return path_radiance_one(c, rays, n64, max_depth, seed, sample, rgb, st);  // devices[0]
+}
+
+int wr_path_radiance_dev(wr_context* c, const wr_ray* rays, int64_t n64, int32_t max_depth, uint32_t seed,
+                         int32_t sample, float* rgb, float* rgb_sq, wr_stats* st) {
+  if (!c) return fail(WR_E_ARG, "null context");
+  if (int rc = check_radiance(c, rays, n64, max_depth, rgb)) return rc;
+  DeviceGuard dg;
+  return path_radiance_one(c, rays, n64, max_depth, seed, sample, rgb, st, true, rgb_sq);  // devices[0]
+}
+
+// The rays of wr_render_features as records (k_camera_rays), at their value index.
+int wr_camera_rays(wr_context* c, int32_t width, int32_t height, int layout, wr_ray* rays, int rays_on_device) {
+  if (!c) return fail(WR_E_ARG, "null context");
+  if (width < 1 || height < 1 || static_cast<int64_t>(width) * height > (int64_t(1) << 28))
+    return fail(WR_E_ARG, "bad film size (1 .. 2^28 pixels)");
+  if (layout != WR_FILM_PT && layout != WR_FILM_BDPT) return fail(WR_E_ARG, "layout must be WR_FILM_PT or WR_FILM_BDPT");
+  if (!rays) return fail(WR_E_ARG, "null rays");
+  const int n = width * height;
+  const size_t bytes = size_t(n) * sizeof(wr_ray);
+  if (rays_on_device)
+    if (int rc = check_dev_range(c, rays, bytes, "rays", "wr_camera_rays with rays_on_device = 0")) return rc;
+  DeviceGuard dg;
+  HIPCHK(hipSetDevice(c->device));
+  wr_ray* dr = rays;
+  if (!rays_on_device) {
+    if (int rc = api_scratch(c, bytes)) return rc;
+    dr = reinterpret_cast<wr_ray*>(c->api_tmp.p);
+  }
+  // after the caller's work on the legacy null stream, like a render
+  (void)hipEventRecord(c->t_null, nullptr);
+  (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
+  const int g = std::max(1, std::min(c->grid, (n + 255) / 256));
+  hipLaunchKernelGGL(k_camera_rays, dim3(g), dim3(256), 0, c->stream, c->ds, width, height, layout, dr);
+  HIPCHK(hipGetLastError());
+  if (!rays_on_device) HIPCHK(hipMemcpyAsync(rays, dr, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return WR_OK;
 }
 
 int wr_create_multi(const wr_scene* sc, const int* devices, int n, wr_context** out) {

@@ -26,7 +26,8 @@ EXPORTS = ["wr_scene_load", "wr_scene_from_desc", "wr_scene_info_get", "wr_scene
            "wr_render_bdpt", "wr_render_path", "wr_render_vcm", "wr_path_radiance", "wr_film_write_ppm",
            "wr_film_write_image", "wr_checkpoint_save", "wr_checkpoint_load", "wr_last_error", "wr_api_version",
            "wr_reserve", "wr_request_hw_queues", "wr_render_bdpt_moments", "wr_render_vcm_moments",
-           "wr_render_path_moments", "wr_film_error", "wr_render_features", "wr_film_denoise"]
+           "wr_render_path_moments", "wr_film_error", "wr_render_features", "wr_film_denoise",
+           "wr_camera_rays", "wr_trace_closest_dev", "wr_occluded_dev", "wr_path_radiance_dev"]
 CKPT_BDPT, CKPT_VCM, CKPT_PT = 1, 2, 3
 FILM_PT, FILM_BDPT = 0, 1
 
@@ -213,6 +214,10 @@ def lib():
         L.wr_film_error.argtypes = [P, P, P, I, I, I, I, P, C.POINTER(WrErrorInfo)]
         L.wr_render_features.argtypes = [P, I, I, I, P, P, P, P, I, C.POINTER(WrStats)]
         L.wr_film_denoise.argtypes = [P, P, P, I, I, I, P, P, P, C.POINTER(WrDenoiseParams), I, P]
+        L.wr_camera_rays.argtypes = [P, I, I, I, P, I]
+        L.wr_trace_closest_dev.argtypes = [P, P, I64, P]
+        L.wr_occluded_dev.argtypes = [P, P, P, I64, P]
+        L.wr_path_radiance_dev.argtypes = [P, P, I64, I, C.c_uint32, I, P, P, C.POINTER(WrStats)]
         L.wr_last_error.restype = C.c_char_p
         _lib = L
     return _lib
@@ -329,6 +334,50 @@ def _host_film(film, height, width):
     return film
 
 
+def _dev_tensor(t, name, shape, dtype, device):
+    """A device array of the _t calls: a torch tensor of exactly this dtype
+    ("float32", "int32", "uint8") and shape (None: any length), C-contiguous,
+    on cuda:`device` (None: not checked).  Anything else raises ValueError --
+    nothing is converted or moved, since an output has to be written in place."""
+    torch = sys.modules.get("torch")
+    if torch is None or not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor on the context's device, got {type(t).__name__} "
+                         "(numpy arrays go to the host calls)")
+    if t.dtype != getattr(torch, dtype):
+        raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+    if t.dim() != len(shape) or any(w is not None and w != g for w, g in zip(shape, t.shape)):
+        want = "(" + ", ".join("n" if w is None else str(w) for w in shape) + ("," if len(shape) == 1 else "") + ")"
+        raise ValueError(f"{name} must have shape {want}, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be C-contiguous (strides {tuple(t.stride())})")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must live on the GPU (is_cuda), got a {t.device} tensor: host arrays go to the "
+                         "host calls")
+    if device is not None and t.device.index != device:
+        raise ValueError(f"{name} is on cuda:{t.device.index}, the context on cuda:{device}")
+    return t
+
+
+def _join_side_stream(device):
+    """The library orders a call after the legacy null stream only: if torch's
+    current stream on the device is another one, wait for it here."""
+    torch = sys.modules["torch"]
+    s = torch.cuda.current_stream(device)
+    if s != torch.cuda.default_stream(device):
+        s.synchronize()
+
+
+def hit_fields(hits):
+    """The fields of (n, 10) int32 wr_hit records (trace_closest_t's tensor, or a
+    numpy array of the same layout) as views: t (n,), p and n (n, 3) float32;
+    prim, inside and mat_id (n,) int32."""
+    if hits.ndim != 2 or hits.shape[1] != 10:
+        raise ValueError(f"hits must have shape (n, 10), got {tuple(hits.shape)}")
+    f32 = np.float32 if isinstance(hits, np.ndarray) else sys.modules["torch"].float32
+    return {"t": hits[:, 0].view(f32), "p": hits[:, 1:4].view(f32), "n": hits[:, 4:7].view(f32),
+            "prim": hits[:, 7], "inside": hits[:, 8], "mat_id": hits[:, 9]}
+
+
 def rays_from_arrays(o, d, tmin=0.0, tmax=1e7):
     n = o.shape[0]
     arr = np.zeros((n, 8), np.float32)
@@ -421,6 +470,94 @@ class Context:
                                 targets.ctypes.data_as(C.POINTER(C.c_float)), n,
                                 out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
+
+    # ---- ray batches that already live on the GPU (wr_*_dev).
+    # Every tensor is validated before the library sees its pointer (ValueError);
+    # nothing is converted, moved or made contiguous.  Stream rule of all _t
+    # calls: the library orders the call after torch's default stream; if
+    # torch's current stream on the device is another one, the wrapper
+    # synchronises that stream first.  The call returns when its outputs are
+    # written, so later torch work on any stream sees them.
+    def _dev_args(self, *specs):
+        """specs: (tensor, name, shape, dtype).  Returns the context's device index."""
+        for t, name, shape, dtype in specs:
+            _dev_tensor(t, name, shape, dtype, None)
+        dev = self.devices()[0]
+        for t, name, shape, dtype in specs:
+            _dev_tensor(t, name, shape, dtype, dev)
+        _join_side_stream(dev)
+        return dev
+
+    def camera_rays(self, width, height, layout=FILM_PT):
+        """wr_camera_rays: the rays render_features traces, one per value index
+        of a width x height film in `layout`, as an (n, 8) float32 numpy array."""
+        rays = np.zeros((width * height, 8), np.float32)
+        check(lib().wr_camera_rays(self.h, width, height, layout, rays.ctypes.data_as(C.c_void_p), 0))
+        return rays
+
+    def camera_rays_t(self, width, height, layout=FILM_PT):
+        """camera_rays as a torch float32 (n, 8) tensor on the context's device,
+        written there (nothing crosses to the host)."""
+        import torch
+        dev = self.devices()[0]
+        rays = torch.empty((width * height, 8), dtype=torch.float32, device=f"cuda:{dev}")
+        _join_side_stream(dev)
+        check(lib().wr_camera_rays(self.h, width, height, layout, C.c_void_p(rays.data_ptr()), 1))
+        return rays
+
+    def trace_closest_t(self, rays, out=None):
+        """wr_trace_closest_dev: rays is a torch float32 (n, 8) tensor on the
+        context's device (o, d, tmin, tmax; d used as given).  Returns an int32
+        (n, 10) tensor of wr_hit records (`out` when given, written in place);
+        hit_fields() names its columns.  If torch's current stream is not the
+        default stream, it is synchronised before the call."""
+        import torch
+        _dev_tensor(rays, "rays", (None, 8), "float32", None)
+        n = rays.shape[0]
+        if out is None:
+            out = torch.empty((n, 10), dtype=torch.int32, device=rays.device)
+        self._dev_args((rays, "rays", (None, 8), "float32"), (out, "out", (n, 10), "int32"))
+        check(lib().wr_trace_closest_dev(self.h, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr())))
+        return out
+
+    def occluded_t(self, rays, targets, out=None):
+        """wr_occluded_dev: rays (n, 8) and targets (n, 3) float32 tensors on the
+        context's device.  Returns a uint8 (n,) tensor (`out` when given).  If
+        torch's current stream is not the default stream, it is synchronised
+        before the call."""
+        import torch
+        _dev_tensor(rays, "rays", (None, 8), "float32", None)
+        n = rays.shape[0]
+        _dev_tensor(targets, "targets", (n, 3), "float32", None)
+        if out is None:
+            out = torch.empty((n,), dtype=torch.uint8, device=rays.device)
+        self._dev_args((rays, "rays", (None, 8), "float32"), (targets, "targets", (n, 3), "float32"),
+                       (out, "out", (n,), "uint8"))
+        check(lib().wr_occluded_dev(self.h, C.c_void_p(rays.data_ptr()), C.c_void_p(targets.data_ptr()), n,
+                                    C.c_void_p(out.data_ptr())))
+        return out
+
+    def path_radiance_t(self, rays, max_depth=7, seed=5489, sample=0, rgb=None, rgb_sq=None):
+        """wr_path_radiance_dev: the radiance of each ray of a torch float32
+        (n, 8) tensor on the context's device, ADDED into rgb ((n, 3) float32; a
+        new zeroed tensor when None) and, squared per value, into rgb_sq (when
+        given): one call per sample index builds the pair film_error reads as
+        an n x 1 film.  Returns (rgb, stats).  If torch's current stream is not
+        the default stream, it is synchronised before the call."""
+        import torch
+        _dev_tensor(rays, "rays", (None, 8), "float32", None)
+        n = rays.shape[0]
+        if rgb is None:
+            rgb = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
+        specs = [(rays, "rays", (None, 8), "float32"), (rgb, "rgb", (n, 3), "float32")]
+        if rgb_sq is not None:
+            specs.append((rgb_sq, "rgb_sq", (n, 3), "float32"))
+        self._dev_args(*specs)
+        st = WrStats()
+        check(lib().wr_path_radiance_dev(self.h, C.c_void_p(rays.data_ptr()), n, max_depth, seed, sample,
+                                         C.c_void_p(rgb.data_ptr()),
+                                         C.c_void_p(rgb_sq.data_ptr()) if rgb_sq is not None else None, C.byref(st)))
+        return rgb, st
 
     def render_bdpt(self, width, height, iterations=1, seed=5489, iter_begin=0, control_length=3,
                     max_path_length=10, faithful=1, time_kernels=0, count_work=0, film=None, film_ptr=None):
