@@ -10,6 +10,9 @@
 #include <cstring>
 #include <atomic>
 #include <future>
+#include <queue>
+#include <utility>
+#include <vector>
 
 #include "wr_scene.h"
 
@@ -677,6 +680,75 @@ struct Collapse8 {
   }
 };
 
+// Top-first node order (wr_bvh.h, build_fast's `top`).  A node's box is the
+// union of its non-empty child boxes; its inner children are the links >= 0.
+inline int child_slots(const BNode&) { return 2; }
+inline int child_slots(const BNode4&) { return 4; }
+inline int child_slots(const BNode4Q&) { return 4; }
+inline bool child_box(const BNode& n, int k, Box& b) {
+  for (int a = 0; a < 3; ++a) {
+    b.lo[a] = n.b[6 * k + a];
+    b.hi[a] = n.b[6 * k + 3 + a];
+  }
+  return !(b.empty() || (b.lo[0] == 3e38f && b.hi[0] == 3e38f));
+}
+inline bool child_box(const BNode4& n, int k, Box& b) {
+  for (int a = 0; a < 3; ++a) {
+    b.lo[a] = n.lo[a][k];
+    b.hi[a] = n.hi[a][k];
+  }
+  return !(b.empty() || (b.lo[0] == 3e38f && b.hi[0] == 3e38f));
+}
+inline bool child_box(const BNode4Q& n, int k, Box& b) {
+  if (n.c[k] == kEmptyLink) return false;
+  for (int a = 0; a < 3; ++a) {
+    b.lo[a] = std::fma(static_cast<float>(n.qlo[a][k]), n.scale[a], n.org[a]);
+    b.hi[a] = std::fma(static_cast<float>(n.qhi[a][k]), n.scale[a], n.org[a]);
+  }
+  return true;
+}
+template <class Node>
+int top_first(std::vector<Node>& nodes, int budget) {
+  const int n = static_cast<int>(nodes.size());
+  if (budget <= 0 || n == 0) return 0;
+  const int ntop = std::min(budget, n);
+  auto area = [&](int i) {
+    Box u, b;
+    for (int k = 0; k < child_slots(nodes[static_cast<size_t>(i)]); ++k)
+      if (child_box(nodes[static_cast<size_t>(i)], k, b)) u.grow(b);
+    return u.area();
+  };
+  // the frontier, largest area first, then the lower build index
+  using Key = std::pair<double, int>;  // (area, -index): the heap's largest
+  std::priority_queue<Key> open;
+  open.push(Key{area(0), 0});
+  std::vector<int> order;  // new index -> build index
+  std::vector<char> taken(static_cast<size_t>(n), 0);
+  order.reserve(static_cast<size_t>(n));
+  while (static_cast<int>(order.size()) < ntop && !open.empty()) {
+    const int i = -open.top().second;
+    open.pop();
+    order.push_back(i);
+    taken[static_cast<size_t>(i)] = 1;
+    const Node& nd = nodes[static_cast<size_t>(i)];
+    for (int k = 0; k < child_slots(nd); ++k)
+      if (nd.c[k] >= 0) open.push(Key{area(nd.c[k]), -nd.c[k]});
+  }
+  for (int i = 0; i < n; ++i)
+    if (!taken[static_cast<size_t>(i)]) order.push_back(i);
+  std::vector<int> at(static_cast<size_t>(n));  // build index -> new index
+  for (int j = 0; j < n; ++j) at[static_cast<size_t>(order[static_cast<size_t>(j)])] = j;
+  std::vector<Node> moved(static_cast<size_t>(n));
+  for (int j = 0; j < n; ++j) {
+    Node nd = nodes[static_cast<size_t>(order[static_cast<size_t>(j)])];
+    for (int k = 0; k < child_slots(nd); ++k)
+      if (nd.c[k] >= 0) nd.c[k] = at[static_cast<size_t>(nd.c[k])];
+    moved[static_cast<size_t>(j)] = nd;
+  }
+  nodes.swap(moved);
+  return ntop;
+}
+
 }  // namespace
 
 // Sphere::hit (sphere.cpp:17-78) forms t = t_ca -+ sqrt(t_hc), t_hc = r^2 -
@@ -693,7 +765,7 @@ struct Collapse8 {
 // the search sends a ray from outside it to the KD walk (wr_fast.h).
 double sphere_grow(double M) { return 3e-5 * M * M + 2.5e-3 * M + 2.0 * 1e-3; }
 
-void build_fast(const wr::Scene& s, FastHost& out, int wide, bool with4) {
+void build_fast(const wr::Scene& s, FastHost& out, int wide, bool with4, int top, int top4) {
   out = FastHost();
   if (s.prims.empty() || s.nodes.empty()) {
     out.why = "empty scene";
@@ -810,9 +882,13 @@ void build_fast(const wr::Scene& s, FastHost& out, int wide, bool with4) {
     if (m < 0) m = nn / 2;
     B.inner(0, nn, m, 1);
   }
+  // the top sets first (the collapses read the binary tree through its links:
+  // the same wide trees from either numbering)
+  if (out.ok) out.ntop = top_first(out.nodes, top);
   if (out.ok && (wide == 4 || with4)) {
     out.nodes4.reserve(out.nodes.size() / 2 + 4);
     Collapse{out}.node(0, 1);
+    out.ntop4 = top_first(out.nodes4, top4);
   }
   if (out.ok && wide == 8) {
     out.nodes8.reserve(out.nodes.size() / 4 + 4);

@@ -167,7 +167,9 @@ struct Scene;
 namespace wrf {
 struct FastHost {
   std::vector<BNode> nodes;
+  int ntop = 0;                 // nodes [0, ntop): the top set (top_first; 0: build order kept)
   std::vector<BNode4S> nodes4;  // the search's tree (root 0)
+  int ntop4 = 0;                // the same for nodes4
   int depth4 = 0;              // deepest 4-wide node chain
   std::vector<BNode8> nodes8;  // WR_BVH_WIDE 8: the search's tree (root 0)
   int depth8 = 0;              // deepest 8-wide node chain
@@ -189,7 +191,25 @@ struct FastHost {
 // data.
 // wide: the search tree built beside the binary one (4: nodes4, 8: nodes8);
 // with4: the 4-wide one as well (a binary-tree scene's latency-bound renders)
-void build_fast(const wr::Scene& s, FastHost& out, int wide = WR_BVH_WIDE, bool with4 = false);
+// top, top4: node budgets of the top sets of nodes / nodes4.  The first
+// min(budget, node count) entries of the array become the parent-closed set
+// grown from the root by opening the frontier node of largest box area first
+// (ties: the lower build index), the rest keep their build order, and every
+// link is rewritten -- the same tree under another numbering.  The search
+// serves those entries from LDS (wr_fast.h); a few KB of them take most of a
+// ray's node visits (torus: 63 nodes 0.55, 127 nodes 0.66, 255 nodes 0.75).
+// 0: build order.  Defaults by measurement (profiles/r14/top_lds): 63 binary
+// nodes (4 KB per workgroup; 127 alike, 255 loses to the LDS it takes from the
+// other pipelines' kernels), none for the 4-wide tree (inside the noise).
+#ifndef WR_BVH_TOP_NODES
+#define WR_BVH_TOP_NODES 63
+#endif
+#ifndef WR_BVH_TOP4_NODES
+#define WR_BVH_TOP4_NODES 0
+#endif
+constexpr int kTopNodes = WR_BVH_TOP_NODES, kTop4Nodes = WR_BVH_TOP4_NODES;
+void build_fast(const wr::Scene& s, FastHost& out, int wide = WR_BVH_WIDE, bool with4 = false, int top = kTopNodes,
+                int top4 = kTop4Nodes);
 // scenes of at least this many triangles search the 4-wide tree (a binary
 // tree of 2^18 triangles is ~28 MB of nodes and records: past the 4 MB L2)
 #ifndef WR_BVH4_MIN_TRIS

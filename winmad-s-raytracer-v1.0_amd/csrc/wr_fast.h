@@ -41,6 +41,7 @@ struct FastScene {
   const float4* nodes4;  // 4 per wrf::BNode4Q / 8 per wrf::BNode4 (wrf::BNode4S: the search when wide == 4)
   const float4* nodes8;  // 8 per wrf::BNode8 (the search when wide == 8)
   int wide;              // the search tree's width: 2 (nodes), 4 (nodes4) or 8 (nodes8)
+  int ntop;              // the search serves nodes [0, ntop) of its tree from LDS (wrf::FastHost::ntop / ntop4; 0: none)
   const float4* tris;   // 3 per wrf::TriRec
   const int* prim_leaf_off;
   const int* prim_leaf;
@@ -124,6 +125,39 @@ __host__ __device__ constexpr int search_lds_stack(int wide) {
 __host__ __device__ constexpr size_t search_lds_bytes(int depth, int wide) {
   return size_t(depth < search_lds_stack(wide) ? depth : search_lds_stack(wide)) * 64 * 6;
 }
+// The search's workgroup: WG waves, and in its dynamic LDS
+//   [top set: nodes [0, ntop) of the search tree][stack columns + RL list buffer] x WG
+// The top set is the parent-closed head of the node array (wrf::build_fast's
+// top-first order): every wave copies its share in, one barrier, and a lane
+// whose node index is below ntop reads the same 64 (4-wide: 128) bytes with
+// ds_read_b128 instead of a global load -- the first steps of a ray's descent
+// then cost an LDS round trip (~50 cycles) instead of an L1 / L2 one (180-225).
+__host__ __device__ constexpr size_t search_node_bytes(int wide) {
+  return wide == 4 ? sizeof(wrf::BNode4S) : wide == 8 ? sizeof(wrf::BNode8) : sizeof(wrf::BNode);
+}
+// (Measured and not kept, DESIGN.md 9: a copy padded to 80 / 144 bytes per
+// node against bank conflicts, alike; a "top phase" in which only lanes inside
+// the top set step while there is one, -25 % on C2.)
+__host__ __device__ constexpr size_t search_top_bytes(int ntop, int wide) { return size_t(ntop) * search_node_bytes(wide); }
+__host__ __device__ constexpr size_t search_wave_bytes(int depth, int wide, bool rl) {
+  return search_lds_bytes(depth, wide) + (rl ? 64 * sizeof(int) : 0);
+}
+__host__ __device__ constexpr size_t search_wg_bytes(int depth, int wide, bool rl, int ntop, int wg) {
+  return search_top_bytes(ntop, wide) + size_t(wg) * search_wave_bytes(depth, wide, rl);
+}
+// 16 bytes of the top set, through a pointer typed as LDS: with a generic
+// pointer the compiler joins the LDS and the global fetch of a node into one
+// flat load behind a pointer select (vmcnt + lgkmcnt waits on every step)
+typedef float wr_f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 lds_load4(const float4* p) {
+  const wr_f4 v = *(const __attribute__((address_space(3))) wr_f4*)(p);
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+constexpr int kMaxSearchWG = 16;  // waves per search workgroup (1024 threads)
+#ifndef WR_SEARCH_WG
+#define WR_SEARCH_WG 4  // waves per workgroup of a search with a top set (env WR_BVH_TOP_WG)
+#endif
+constexpr int kSearchWG = WR_SEARCH_WG;
 // spill entries per lane for a search stack of `depth` entries
 __host__ __device__ constexpr size_t search_spill_entries(int depth, int wide) {
   return depth > search_lds_stack(wide) ? size_t(depth - search_lds_stack(wide)) : 0;
@@ -1425,12 +1459,22 @@ __device__ __forceinline__ bool first_cells_crossed(const FastScene& F, int p1, 
 // reads those rays only.  The test is the resolve's own, on the same floats.
 template <bool COUNT, int W, bool SPH, bool RL = false>
 __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F, const TraceQueues& Q, int* fetch,
-                                           float* t2buf, int2* pairs, int2* spill, uint32_t* lds, FastCounters& ctr,
-                                           int bid, int nblk,  // this block's index among the launch's nblk search blocks
+                                           float* t2buf, int2* pairs, int2* spill, uint32_t* smem, FastCounters& ctr,
+                                           int wgid, int nwg,  // this workgroup's index among the launch's nwg
                                            int* rlist = nullptr, int* rlist_n = nullptr) {
   constexpr int kLdsStack = SearchStack<W>::lds;
   constexpr bool kSearchSpills = SearchStack<W>::spills;
   const int lane = __lane_id();
+  // the workgroup's waves (search_wg_bytes); bid / nblk: this wave's index
+  // among the launch's nblk search waves
+  const int wg = static_cast<int>(blockDim.x) >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+  const int bid = wgid * wg + wave, nblk = nwg * wg;
+  // (the 8-wide and the quantised 4-wide build options search without a top set: the host gives them ntop 0)
+  const int ntop = (W == 8 || (W == 4 && WR_BVH4_QUANT)) ? 0 : F.ntop;
+  const float4* const top = reinterpret_cast<const float4*>(smem);
+  constexpr int kTop4 = static_cast<int>(search_node_bytes(W) / 16);  // float4 per node
+  uint32_t* const lds = smem + (search_top_bytes(ntop, W) + wave * search_wave_bytes(F.sdepth, W, RL)) / 4;
   int* stk_link = reinterpret_cast<int*>(lds) + lane;
   uint16_t* stk_t = reinterpret_cast<uint16_t*>(reinterpret_cast<int*>(lds) + min(F.sdepth, kLdsStack) * 64) + lane;
   const size_t gl = static_cast<size_t>(nblk) * 64, gidx = static_cast<size_t>(bid) * 64 + lane;
@@ -1446,6 +1490,18 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
 #define WR_GRAB_ADAPT 1
 #endif
   const int grab = WR_GRAB_ADAPT && n <= 64 * nblk ? 64 : kRayGrab;
+  // A workgroup none of whose waves gets a ray leaves before the copy (a
+  // launch of few rays does not pay it there): the test is on the
+  // workgroup's first wave, so every wave of the workgroup decides alike and
+  // none waits at a barrier another has skipped.  Per wave only after it.
+  if (wgid * wg * grab >= n) return;
+  if (ntop > 0) {
+    const float4* const src = W == 4 ? F.nodes4 : F.nodes;
+    float4* const dst = reinterpret_cast<float4*>(smem);
+    const int words = ntop * kTop4;
+    for (int i = static_cast<int>(threadIdx.x); i < words; i += static_cast<int>(blockDim.x)) dst[i] = src[i];
+    __syncthreads();
+  }
   if (bid * grab >= n) return;
   int r = -1, qi = 0, lidx = 0;
   bool pool = true;
@@ -1647,9 +1703,20 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
         float k2 = slabq(2, lk.z);
         float k3 = slabq(3, lk.w);
 #else
-        const float4* np = F.nodes4 + 8 * static_cast<size_t>(cur);
-        const float4 bx0 = np[0], by0 = np[1], bz0 = np[2], bx1 = np[3], by1 = np[4], bz1 = np[5];
-        const int4 lk = *reinterpret_cast<const int4*>(np + 6);
+        // (from the LDS copy when in the top set, as the binary node below)
+        float4 bx0, by0, bz0, bx1, by1, bz1;
+        int4 lk;
+        if (cur < ntop) {
+          const float4* tp = top + kTop4 * cur;
+          bx0 = lds_load4(tp), by0 = lds_load4(tp + 1), bz0 = lds_load4(tp + 2);
+          bx1 = lds_load4(tp + 3), by1 = lds_load4(tp + 4), bz1 = lds_load4(tp + 5);
+          const float4 l = lds_load4(tp + 6);
+          lk = make_int4(__float_as_int(l.x), __float_as_int(l.y), __float_as_int(l.z), __float_as_int(l.w));
+        } else {
+          const float4* np = F.nodes4 + 8 * static_cast<size_t>(cur);
+          bx0 = np[0], by0 = np[1], bz0 = np[2], bx1 = np[3], by1 = np[4], bz1 = np[5];
+          lk = *reinterpret_cast<const int4*>(np + 6);
+        }
         auto slab4 = [&](float lx, float ly, float lz, float hx, float hy, float hz) {
           const float x0 = fmaf(lx, binv.x, cl.x), x1 = fmaf(hx, binv.x, ch.x);
           const float y0 = fmaf(ly, binv.y, cl.y), y1 = fmaf(hy, binv.y, ch.y);
@@ -1748,9 +1815,26 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
           cur = lk8[0];
         }
         } else {
-        const float4* np = F.nodes + 4 * static_cast<size_t>(cur);
-        const float4 n0 = np[0], n1 = np[1], n2 = np[2];
-        const int4 lk = *reinterpret_cast<const int4*>(np + 3);
+        // the node: from the workgroup's LDS copy when in the top set (the
+        // same 64 bytes), else from global memory.  Two branches, each with
+        // its own loads: an iteration in which no lane takes the global one
+        // issues no vector-memory load
+        float4 n0, n1, n2;
+        int4 lk;
+        if (cur < ntop) {
+          const float4* tp = top + kTop4 * cur;
+          n0 = lds_load4(tp);
+          n1 = lds_load4(tp + 1);
+          n2 = lds_load4(tp + 2);
+          const float4 l = lds_load4(tp + 3);
+          lk = make_int4(__float_as_int(l.x), __float_as_int(l.y), __float_as_int(l.z), __float_as_int(l.w));
+        } else {
+          const float4* np = F.nodes + 4 * static_cast<size_t>(cur);
+          n0 = np[0];
+          n1 = np[1];
+          n2 = np[2];
+          lk = *reinterpret_cast<const int4*>(np + 3);
+        }
         auto slab = [&](float lx, float ly, float lz, float hx, float hy, float hz, float& tn) {
           const float x0 = fmaf(lx, binv.x, cl.x), x1 = fmaf(hx, binv.x, ch.x);
           const float y0 = fmaf(ly, binv.y, cl.y), y1 = fmaf(hy, binv.y, ch.y);

@@ -307,8 +307,10 @@ __device__ __forceinline__ void fast_counts(DevCounters* ctr, const FastCounters
 // that the triangle scenes' search keeps its registers
 // RL: the search settles the rays whose winner's membership its first leaf
 // cells prove (the resolve's first test) and lists the rest for k_fast_resolve
+// The workgroup is 1 to kMaxSearchWG waves (the launch's choice, wr_fast.h
+// search_wg_bytes); the register budget is amdgpu_waves_per_eu's as before.
 template <bool COUNT, int W, bool SPH, bool RL = false>
-__global__ void __launch_bounds__(kTraceBlock)
+__global__ void __launch_bounds__(kTraceBlock * kMaxSearchWG)
 __attribute__((amdgpu_waves_per_eu(W == 4 ? WR_FAST4_WAVES : WR_FAST_WAVES, 8))) WR_NO_PK_FP32
 k_trace_fast(DevScene S, FastScene F, TraceQueues Q, DevCounters* ctr, int* fetch, float* t2buf, int2* pairs,
              int2* spill, int* rlist, int* rlist_n) {
@@ -320,8 +322,6 @@ k_trace_fast(DevScene S, FastScene F, TraceQueues Q, DevCounters* ctr, int* fetc
 }
 // the search kernel for a tree width (instantiated for 2 and 4; 8 when the
 // library is built with WR_BVH_WIDE=8)
-// RL: the search's per-wave buffer of listed rays (trace_fast)
-constexpr size_t kRlistLds = 64 * sizeof(int);
 using TraceFastKernel = void (*)(DevScene, FastScene, TraceQueues, DevCounters*, int*, float*, int2*, int2*, int*,
                                  int*);
 template <bool COUNT>
@@ -785,7 +785,11 @@ struct wr_context {
   Arena fast_mem;
   bool fast_ok = false;   // scene supports it
   bool fast_on = false;   // WR_TRACE_BVH mode selected
-  int fast_blocks = 4096; // resident one-wave workgroups of k_trace_fast
+  int fast_blocks = 4096; // resident waves of k_trace_fast (a multiple of search_wg)
+  // the search's workgroup (wr_fast.h search_wg_bytes): its waves, and the top
+  // set of the 4-wide tree of search_scene (fs.ntop: the tree fs searches)
+  int search_wg = 1;
+  int ntop4 = 0;
   int resolve_blocks = 0; // k_fast_resolve's one-wave workgroups (0: fast_blocks; env WR_RESOLVE_GRID per CU)
   bool resolve_list = true;  // the search lists the rays the resolve must see (env WR_RESOLVE_LIST=0: all rays)
   bool verify = false;      // WR_BVH_VERIFY=1: every BVH answer checked against the KD walk
@@ -1325,6 +1329,7 @@ FastScene search_scene(const wr_context* c) {
   if (c->wide_now == 4 && c->fs4_ok) {
     F.wide = 4;
     F.sdepth = c->sdepth4;
+    F.ntop = c->ntop4;
   }
   return F;
 }
@@ -1346,8 +1351,13 @@ int trace_launch(wr_context* c, hipStream_t stream, DevCounters* ctr, const Trac
   if (c->fast_on && !c->stamps && ts.t2 && static_cast<size_t>(max_rays) <= ts.t2_cap) {
     const FastScene F = search_scene(c);  // the render's search tree
     const int blocks = (max_rays + kTraceBlock - 1) / kTraceBlock;
-    const int fgrid = std::max(1, std::min(c->fast_blocks, blocks));
-    const size_t lds = fast_lds_bytes(c->fs.depth), slds = search_lds_bytes(F.sdepth, F.wide);
+    // the search's waves in workgroups of search_wg (fast_blocks is a
+    // multiple of it: the spill area holds fast_blocks waves)
+    // A tree searched without a top set keeps one wave per workgroup: a small
+    // launch then spreads its waves over the CUs instead of packing them by fours.
+    const int wg = F.ntop > 0 ? c->search_wg : 1;
+    const int fgrid = (std::max(1, std::min(c->fast_blocks, blocks)) + wg - 1) / wg;
+    const size_t lds = fast_lds_bytes(c->fs.depth);
     // the search settles the rays its first membership test proves and lists
     // the rest for the resolve (in the t2 region: t2 is kept by diagnostics
     // only).  Measured (profiles/r5/resolve_list): C4 +5 %, C2 +1 %, VCM +1 %;
@@ -1355,7 +1365,7 @@ int trace_launch(wr_context* c, hipStream_t stream, DevCounters* ctr, const Trac
     const bool rl = c->resolve_list && !F.diag && !F.sph && F.wide != 8 && mode != TRACE_DENSE;
     int* rlist = rl ? reinterpret_cast<int*>(ts.t2) : nullptr;
     int* rlist_n = rl ? ts.rlist_n : nullptr;
-    const size_t rlds = slds + (rl ? kRlistLds : 0);
+    const size_t rlds = search_wg_bytes(F.sdepth, F.wide, rl, F.ntop, wg);
     // the search's pair records of near-ties (kPairWindow): after the lists
     int2* pairs = reinterpret_cast<int2*>(ts.t2 + 2 * ts.t2_cap);
     hipEvent_t f0 = nullptr, f1 = nullptr, fa = nullptr, fb = nullptr;
@@ -1367,7 +1377,7 @@ int trace_launch(wr_context* c, hipStream_t stream, DevCounters* ctr, const Trac
       (void)hipEventRecord(f0, stream);
     }
     auto kf = count ? trace_fast_kernel<true>(F.wide, F.sph, rl) : trace_fast_kernel<false>(F.wide, F.sph, rl);
-    hipLaunchKernelGGL(kf, dim3(fgrid), dim3(kTraceBlock), rlds, stream, c->ds, F, Q, ctr, fetch, ts.t2, pairs,
+    hipLaunchKernelGGL(kf, dim3(fgrid), dim3(kTraceBlock * wg), rlds, stream, c->ds, F, Q, ctr, fetch, ts.t2, pairs,
                        ts.spill, rlist, rlist_n);
     if (c->trace_log) (void)hipEventRecord(fa, stream);
     int* hard = reinterpret_cast<int*>(ts.t2 + ts.t2_cap);
@@ -1901,6 +1911,10 @@ struct SceneKnobs {
   int trace_bvh = -1;          // 0: contexts start in the reference KD walk
   int bvh_diag = 0;
   int bvh_verify = -1;
+  // the search's top set in LDS (wr_fast.h search_wg_bytes): node budgets of
+  // the binary and the 4-wide tree (0: none; WR_BVH_TOP=0 alone is the
+  // one-wave launch without a copy) and the waves per workgroup
+  int bvh_top = -1, bvh_top4 = -1, bvh_top_wg = -1;
 };
 static SceneKnobs read_scene_knobs() {
   SceneKnobs k;
@@ -1913,6 +1927,9 @@ static SceneKnobs read_scene_knobs() {
   if (const char* e = std::getenv("WR_TRACE_BVH")) k.trace_bvh = std::atoi(e) != 0;
   if (const char* e = std::getenv("WR_BVH_DIAG")) k.bvh_diag = std::atoi(e);
   if (const char* e = std::getenv("WR_BVH_VERIFY")) k.bvh_verify = std::atoi(e) != 0;
+  if (const char* e = std::getenv("WR_BVH_TOP")) k.bvh_top = std::max(0, std::min(1024, std::atoi(e)));
+  if (const char* e = std::getenv("WR_BVH_TOP4")) k.bvh_top4 = std::max(0, std::min(512, std::atoi(e)));
+  if (const char* e = std::getenv("WR_BVH_TOP_WG")) k.bvh_top_wg = std::max(1, std::min(kMaxSearchWG, std::atoi(e)));
   return k;
 }
 
@@ -2000,7 +2017,11 @@ static int bvh_width(const wr::Scene& s, const SceneKnobs& k) {
 static int upload_bvh(wr_context& c, const wr::Scene& s, const wr::SceneFlat& f, const SceneKnobs& k) {
   const int wide = bvh_width(s, k);
   wrf::FastHost fh;
-  wrf::build_fast(s, fh, wide, wide == 2);
+  // the top sets' budgets: WR_BVH_TOP / WR_BVH_TOP4, else the build's defaults
+  // (the quantised 4-wide and the 8-wide build options search without one)
+  const int top = k.bvh_top >= 0 ? k.bvh_top : wrf::kTopNodes;
+  const int top4 = WR_BVH4_QUANT ? 0 : k.bvh_top4 >= 0 ? k.bvh_top4 : k.bvh_top == 0 ? 0 : wrf::kTop4Nodes;
+  wrf::build_fast(s, fh, wide, wide == 2, top, top4);
   if (!fh.ok) return WR_OK;
   FastScene& fs = c.fs;
   Upload up;
@@ -2039,21 +2060,49 @@ static int upload_bvh(wr_context& c, const wr::Scene& s, const wr::SceneFlat& f,
   fs.pair = k.pair_record >= 0 ? k.pair_record : 2;
   fs.diag = k.bvh_diag;
   c.fast_ok = true;
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fast_kernel<false>(wide, fs.sph, c.resolve_list), kTraceBlock,
-                                                   search_lds_bytes(fs.sdepth, wide) + (c.resolve_list ? kRlistLds : 0)) != hipSuccess ||
+  // the search's workgroup: one wave and no copy without a top set (the
+  // launch as it was before the top set), else WR_BVH_TOP_WG waves, fewer
+  // where a deep tree's stack columns would outgrow the CU's LDS
+  fs.ntop = wide == 4 ? fh.ntop4 : wide == 2 ? fh.ntop : 0;
+  c.ntop4 = c.fs4_ok ? fh.ntop4 : 0;
+  int wg = k.bvh_top_wg > 0 ? k.bvh_top_wg : (fs.ntop > 0 || c.ntop4 > 0) ? kSearchWG : 1;
+  constexpr size_t kCuLds = 160 * 1024;
+  auto wg_bytes = [&](int w) {
+    size_t b = search_wg_bytes(fs.sdepth, wide, true, fs.ntop, w);
+    if (c.fs4_ok) b = std::max(b, search_wg_bytes(c.sdepth4, 4, true, c.ntop4, w));
+    return b;
+  };
+  while (wg > 1 && wg_bytes(wg) > kCuLds) wg /= 2;
+  if (wg_bytes(wg) > kCuLds) return fail(WR_E_ARG, "the search's top set and stack outgrow the LDS");
+  c.search_wg = wg;
+  // a workgroup of more than 64 KB of dynamic LDS asks for it per kernel
+  if (wg_bytes(wg) > 64 * 1024)
+    for (int cnt = 0; cnt < 2; ++cnt)
+      for (int rl = 0; rl < 2; ++rl)
+        for (int w : {wide, c.fs4_ok ? 4 : wide}) {
+          const TraceFastKernel kf = cnt ? trace_fast_kernel<true>(w, fs.sph, rl) : trace_fast_kernel<false>(w, fs.sph, rl);
+          HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     static_cast<int>(wg_bytes(wg))));
+        }
+  const size_t wgb = search_wg_bytes(fs.sdepth, wide, c.resolve_list, fs.ntop, wg);
+  int per_cu = 0;  // workgroups
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fast_kernel<false>(wide, fs.sph, c.resolve_list),
+                                                   kTraceBlock * wg, wgb) != hipSuccess ||
       per_cu <= 0)
-    per_cu = 8;
-  if (k.fast_waves_per_cu > 0) per_cu = std::min(per_cu, k.fast_waves_per_cu);
-  c.fast_blocks = c.cus * per_cu;
+    per_cu = std::max(1, std::min(8 / wg, static_cast<int>(kCuLds / wgb)));
+  int waves_per_cu = per_cu * wg;
+  if (k.fast_waves_per_cu > 0) waves_per_cu = std::max(wg, std::min(waves_per_cu, k.fast_waves_per_cu) / wg * wg);
+  c.fast_blocks = c.cus * waves_per_cu;
   // the verified BVH is the default traversal (same answers as the KD
   // walk); WR_TRACE_BVH=0 selects the walk
   c.fast_on = k.trace_bvh != 0;
   if (k.bvh_verify >= 0) c.verify = k.bvh_verify != 0;
   if (c.trace_log)
-    std::fprintf(stderr, "[wr bvh] nodes %zu tris %zu depth %d lds %zu B/wave, %d waves/CU -> grid %d; kd grid %d\n",
-                 fh.nodes.size(), fh.tris.size(), fs.sdepth, search_lds_bytes(fs.sdepth, wide), per_cu, c.fast_blocks,
-                 c.trace_blocks);
+    std::fprintf(stderr,
+                 "[wr bvh] nodes %zu tris %zu depth %d lds %zu B/wave, ntop %d (4-wide %d) WG %d waves, %zu B LDS/workgroup, "
+                 "%d waves/CU -> grid %d waves; kd grid %d\n",
+                 fh.nodes.size(), fh.tris.size(), fs.sdepth, search_lds_bytes(fs.sdepth, wide), fs.ntop, c.ntop4, wg, wgb,
+                 waves_per_cu, c.fast_blocks, c.trace_blocks);
   return WR_OK;
 }
 
