@@ -469,6 +469,108 @@ int wr_path_radiance_dev(wr_context* ctx, const wr_ray* rays, int64_t n, int32_t
  * _dev calls.  WR_E_ARG: as wr_render_features; null rays. */
 int wr_camera_rays(wr_context* ctx, int32_t width, int32_t height, int layout, wr_ray* rays, int rays_on_device);
 
+/* ---- shading on device arrays (no reference counterpart).
+ * Callers detect these entry points by their symbols (WR_API_VERSION stays 8).
+ *
+ * What the reference's integrators do at a path vertex, one record per array
+ * element: build the BSDF of a hit and evaluate or sample it, pick a point on
+ * an area light, read an emitter's radiance, draw from the counter RNG.  The
+ * kernels run the device functions the renders run (csrc/wr_devmath.h), so
+ * every value is the render's, and the oracle's, bit for bit.  With
+ * wr_trace_closest_dev / wr_occluded_dev a caller writes its own integrator
+ * over arrays that never leave the GPU.
+ *
+ * Records are plain structs of 4-byte members and need only 4-byte alignment
+ * (a slice out + 1 is fine).  A field the reference leaves unwritten on the
+ * branch a record takes (cos_wo when BSDF::f returns early, wo of a black
+ * sample, ...) is 0: every record starts from zeros. */
+typedef struct {
+  int32_t valid;        /* 0: no BSDF here (see below); the whole record and the call's `out` record are zero */
+  int32_t is_delta;     /* isDelta                                                  */
+  float cos_wi;         /* wiLocal.z                                                */
+  float continue_prob;  /* continueProb                                             */
+  float fresnel;        /* reflectCoeff                                             */
+  float prob[4];        /* diffuse, glossy, reflect, refract                        */
+} wr_bsdf_info;         /* 36 bytes: BSDF::init, bsdf.h:66-89                       */
+typedef struct {
+  float f[3];           /* BSDF::f (bsdf.cpp:102-126)                               */
+  float cos_wo;         /* ... its cosWo                                            */
+  float dir_pdf;        /* ... its directPdfW                                       */
+  float rev_pdf;        /* ... its reversePdfW                                      */
+  float pdf;            /* BSDF::pdf forward (:165-181)                             */
+  float pdf_rev;        /* BSDF::pdf reverse                                        */
+} wr_bsdf_eval;         /* 32 bytes                                                 */
+typedef struct {
+  float f[3];           /* BSDF::sample (bsdf.cpp:183-334)                          */
+  float wo[3];          /* world direction, as sampled (unit up to rounding)        */
+  float pdf;
+  float cos_wo;
+  int32_t type;         /* the T_* bit r3[2] chose: 1 reflect, 2 refract, 4 diffuse, 8 glossy */
+} wr_bsdf_sample;       /* 36 bytes                                                 */
+typedef struct {
+  float le[3];          /* AreaLight::illuminance (light.cpp:4-38)                  */
+  float dir[3];         /* dirToLight                                               */
+  float dist;
+  float direct_pdf;     /* directPdfW                                               */
+  float emission_pdf;   /* emissionPdfW                                             */
+  float cos_light;      /* cosAtLight                                               */
+} wr_light_illum;       /* 40 bytes                                                 */
+typedef struct {
+  float le_cos[3];      /* AreaLight::emit (light.cpp:40-67): radiance * cos        */
+  float pos[3];
+  float dir[3];
+  float emission_pdf;   /* emissionPdfW                                             */
+  float direct_pdf_a;   /* directPdfA                                               */
+  float cos_light;      /* cosAtLight                                               */
+} wr_light_emission;    /* 48 bytes                                                 */
+typedef struct {
+  float le[3];          /* AreaLight::getRadiance (light.cpp:69-100)                */
+  float direct_pdf_a;
+  float emission_pdf;
+} wr_light_rad;         /* 20 bytes                                                 */
+/* BSDF calls.  hits: records as wr_trace_closest_dev writes them; only n,
+ *   mat_id and prim are read.  wi: 3 floats per record, the direction the
+ *   integrators hand to the BSDF constructor (-ray.d); it is normalised in
+ *   the local frame.  wo (eval): 3 floats, a world direction.  r3 (sample):
+ *   3 floats in [0, 1), r3[2] picks the component.  info (or NULL) receives
+ *   the BSDF itself.
+ *   valid = 0 and all-zero records: a miss (prim < 0), material 0, or wi
+ *   within EPS of the tangent plane (bsdf.h:75).  An emitter hit (mat_id < 0)
+ *   is valid with the values the renders use: probabilities 0, continue_prob
+ *   0, not delta, f = 0.
+ * Light calls.  light: an index into Scene::lights (wr_scene_info.nlights).
+ *   illuminate: pos = the shaded point, r3 = the triangle sample.  emit:
+ *   dir_r3 and pos_r3 as AreaLight::emit's two samples.  radiance: the light
+ *   is the hit's (-mat_id - 1), ray_d the direction of the ray that hit it; a
+ *   miss or a non-emitter gives zeros.  WR_E_SCENE on a scene without lights.
+ * wr_rng_uniform_dev: record k receives draws ctr[k]+1 .. ctr[k]+draws of
+ *   stream (seed, iteration, subpath, path[k]) as RNG::randFloat values
+ *   (k / 2^24), out[k * draws + j], and ctr[k] advances by draws.  path NULL:
+ *   path k = k; ctr NULL: counters start at 0 and are not kept.  draws = 3 is
+ *   one RNG::randVector3.  A caller that keeps the counters reproduces the
+ *   path tracer's draw order: subpath 2, path = ray index (wr_path_radiance).
+ * Caller data never becomes a GPU fault: the arrays are on the device, so the
+ *   kernels check them.  A light outside [0, nlights) or a mat_id outside
+ *   (-nlights - 1, nmaterials) gives an all-zero record (valid = 0), not an
+ *   error return.
+ * Ownership, alignment, stream ordering, returning when the outputs are
+ *   written, and devices[0] of a multi-device context: as the _dev calls
+ *   above.  n == 0 succeeds.  WR_E_ARG: a null pointer with n > 0 (except
+ *   the optional ones); n < 0 or n > 2^28; draws outside 1..64; a pointer that
+ *   is not device memory of the context's device; an output range that
+ *   overlaps an input or another output (ctr is in/out). */
+int wr_bsdf_eval_dev(wr_context* ctx, const wr_hit* hits, const float* wi, const float* wo, int64_t n,
+                     wr_bsdf_info* info, wr_bsdf_eval* out);
+int wr_bsdf_sample_dev(wr_context* ctx, const wr_hit* hits, const float* wi, const float* r3, int64_t n,
+                       wr_bsdf_info* info, wr_bsdf_sample* out);
+int wr_light_illuminate_dev(wr_context* ctx, const int32_t* light, const float* pos, const float* r3, int64_t n,
+                            wr_light_illum* out);
+int wr_light_emit_dev(wr_context* ctx, const int32_t* light, const float* dir_r3, const float* pos_r3, int64_t n,
+                      wr_light_emission* out);
+int wr_light_radiance_dev(wr_context* ctx, const wr_hit* hits, const float* ray_d, int64_t n, wr_light_rad* out);
+int wr_rng_uniform_dev(wr_context* ctx, uint32_t seed, uint32_t iteration, uint32_t subpath, const uint32_t* path,
+                       uint32_t* ctr, int32_t draws, int64_t n, float* out);
+
 /* ---- output (ImageFilm::outputImage, scene/film.cpp:39-64; BDPT transpose
  * bidirPathTracing.cpp:29-46) ---- scale -> clamp [0,1] -> pow(1/gamma) ->
  * (uchar)(x*255.0); binary PPM (RGB).  transpose != 0 swaps [i][j] <-> [j][i]

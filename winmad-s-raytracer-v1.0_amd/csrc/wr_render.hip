@@ -542,6 +542,8 @@ __global__ void __launch_bounds__(256) WR_NO_PK_FP32 k_feat_finish(DevScene S, i
 #include "wr_vcm.h"
 static_assert(sizeof(VcmGroup) <= 4000, "kernel argument block too large");
 #include "wr_pt.h"
+// =============================================================== shading on device arrays
+#include "wr_shade.h"
 
 }  // namespace
 
@@ -3578,6 +3580,144 @@ int wr_camera_rays(wr_context* c, int32_t width, int32_t height, int layout, wr_
   if (!rays_on_device) HIPCHK(hipMemcpyAsync(rays, dr, bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return WR_OK;
+}
+
+// ---- shading on device arrays (wr_bsdf_*_dev, wr_light_*_dev, wr_rng_uniform_dev;
+// DESIGN.md 13; kernels in wr_shade.h).  The arguments are checked as those of
+// the _dev calls above, on the host and before any HIP call where that is
+// possible; the indices inside the arrays are checked by the kernels.
+struct ShadeArg {
+  const void* p;
+  size_t rec;  // bytes per record
+  const char* name;
+  bool out;       // written (in/out counts): must not overlap any other array
+  bool optional;  // may be null
+};
+// WR_OK and *grid = 0: nothing to do (n == 0), else the launch grid.
+static int shade_begin(wr_context* c, const char* call, int64_t n, bool lights, std::initializer_list<ShadeArg> args,
+                       int* grid) {
+  *grid = 0;
+  const std::string who = std::string(call) + ": ";
+  if (!c) return fail(WR_E_ARG, who + "null context");
+  if (n < 0) return fail(WR_E_ARG, who + "n < 0");
+  if (n == 0) return WR_OK;
+  if (n > (int64_t(1) << 28)) return fail(WR_E_ARG, who + "at most 2^28 records per call");
+  for (const ShadeArg& a : args)
+    if (!a.p && !a.optional) return fail(WR_E_ARG, who + "null " + a.name);
+  if (lights && c->ds.nlights <= 0) return fail(WR_E_SCENE, who + "the scene has no area light");
+  const size_t nb = static_cast<size_t>(n);
+  for (const ShadeArg& a : args)
+    if (a.p)
+      if (int rc = check_dev_range(c, a.p, nb * a.rec, (who + a.name).c_str(), "no shading call: copy it to the device"))
+        return rc;
+  for (const ShadeArg& a : args)
+    for (const ShadeArg& b : args)
+      if (&a < &b && (a.out || b.out) && ranges_overlap(a.p, nb * a.rec, b.p, nb * b.rec))
+        return fail(WR_E_ARG, who + a.name + " overlaps " + b.name);
+  // a block per 256 records (at most 2^20 blocks): the records cost unequal time, and blocks
+  // that come and go balance the CUs better than c->grid resident ones looping
+  *grid = static_cast<int>((n + 255) / 256);
+  return WR_OK;
+}
+// the context's device current, its stream after the caller's work on the legacy null stream (like a render)
+static int shade_order(wr_context* c) {
+  HIPCHK(hipSetDevice(c->device));
+  (void)hipEventRecord(c->t_null, nullptr);
+  (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
+  return WR_OK;
+}
+static int shade_end(wr_context* c) {
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return WR_OK;
+}
+
+int wr_bsdf_eval_dev(wr_context* c, const wr_hit* hits, const float* wi, const float* wo, int64_t n,
+                     wr_bsdf_info* info, wr_bsdf_eval* out) {
+  int g;
+  if (int rc = shade_begin(c, "wr_bsdf_eval_dev", n, false,
+                           {{hits, sizeof(wr_hit), "hits", false, false}, {wi, 12, "wi", false, false},
+                            {wo, 12, "wo", false, false}, {info, sizeof(wr_bsdf_info), "info", true, true},
+                            {out, sizeof(wr_bsdf_eval), "out", true, false}}, &g))
+    return rc;
+  if (!g) return WR_OK;
+  DeviceGuard dg;
+  if (int rc = shade_order(c)) return rc;
+  hipLaunchKernelGGL(k_bsdf_eval, dim3(g), dim3(256), 0, c->stream, c->ds, c->nmats, hits, wi, wo, n, info, out);
+  return shade_end(c);
+}
+
+int wr_bsdf_sample_dev(wr_context* c, const wr_hit* hits, const float* wi, const float* r3, int64_t n,
+                       wr_bsdf_info* info, wr_bsdf_sample* out) {
+  int g;
+  if (int rc = shade_begin(c, "wr_bsdf_sample_dev", n, false,
+                           {{hits, sizeof(wr_hit), "hits", false, false}, {wi, 12, "wi", false, false},
+                            {r3, 12, "r3", false, false}, {info, sizeof(wr_bsdf_info), "info", true, true},
+                            {out, sizeof(wr_bsdf_sample), "out", true, false}}, &g))
+    return rc;
+  if (!g) return WR_OK;
+  DeviceGuard dg;
+  if (int rc = shade_order(c)) return rc;
+  hipLaunchKernelGGL(k_bsdf_sample, dim3(g), dim3(256), 0, c->stream, c->ds, c->nmats, hits, wi, r3, n, info, out);
+  return shade_end(c);
+}
+
+int wr_light_illuminate_dev(wr_context* c, const int32_t* light, const float* pos, const float* r3, int64_t n,
+                            wr_light_illum* out) {
+  int g;
+  if (int rc = shade_begin(c, "wr_light_illuminate_dev", n, true,
+                           {{light, 4, "light", false, false}, {pos, 12, "pos", false, false},
+                            {r3, 12, "r3", false, false}, {out, sizeof(wr_light_illum), "out", true, false}}, &g))
+    return rc;
+  if (!g) return WR_OK;
+  DeviceGuard dg;
+  if (int rc = shade_order(c)) return rc;
+  hipLaunchKernelGGL(k_light_illuminate, dim3(g), dim3(256), 0, c->stream, c->ds, light, pos, r3, n, out);
+  return shade_end(c);
+}
+
+int wr_light_emit_dev(wr_context* c, const int32_t* light, const float* dir_r3, const float* pos_r3, int64_t n,
+                      wr_light_emission* out) {
+  int g;
+  if (int rc = shade_begin(c, "wr_light_emit_dev", n, true,
+                           {{light, 4, "light", false, false}, {dir_r3, 12, "dir_r3", false, false},
+                            {pos_r3, 12, "pos_r3", false, false},
+                            {out, sizeof(wr_light_emission), "out", true, false}}, &g))
+    return rc;
+  if (!g) return WR_OK;
+  DeviceGuard dg;
+  if (int rc = shade_order(c)) return rc;
+  hipLaunchKernelGGL(k_light_emit, dim3(g), dim3(256), 0, c->stream, c->ds, light, dir_r3, pos_r3, n, out);
+  return shade_end(c);
+}
+
+int wr_light_radiance_dev(wr_context* c, const wr_hit* hits, const float* ray_d, int64_t n, wr_light_rad* out) {
+  int g;
+  if (int rc = shade_begin(c, "wr_light_radiance_dev", n, true,
+                           {{hits, sizeof(wr_hit), "hits", false, false}, {ray_d, 12, "ray_d", false, false},
+                            {out, sizeof(wr_light_rad), "out", true, false}}, &g))
+    return rc;
+  if (!g) return WR_OK;
+  DeviceGuard dg;
+  if (int rc = shade_order(c)) return rc;
+  hipLaunchKernelGGL(k_light_radiance, dim3(g), dim3(256), 0, c->stream, c->ds, hits, ray_d, n, out);
+  return shade_end(c);
+}
+
+int wr_rng_uniform_dev(wr_context* c, uint32_t seed, uint32_t iteration, uint32_t subpath, const uint32_t* path,
+                       uint32_t* ctr, int32_t draws, int64_t n, float* out) {
+  if (c && (draws < 1 || draws > 64)) return fail(WR_E_ARG, "wr_rng_uniform_dev: draws must be 1..64");
+  int g;
+  if (int rc = shade_begin(c, "wr_rng_uniform_dev", n, false,
+                           {{path, 4, "path", false, true}, {ctr, 4, "ctr", true, true},
+                            {out, 4 * static_cast<size_t>(draws), "out", true, false}}, &g))
+    return rc;
+  if (!g) return WR_OK;
+  DeviceGuard dg;
+  if (int rc = shade_order(c)) return rc;
+  hipLaunchKernelGGL(k_rng_uniform, dim3(g), dim3(256), 0, c->stream, seed, iteration, subpath, path, ctr, draws, n,
+                     out);
+  return shade_end(c);
 }
 
 int wr_create_multi(const wr_scene* sc, const int* devices, int n, wr_context** out) {

@@ -27,7 +27,9 @@ EXPORTS = ["wr_scene_load", "wr_scene_from_desc", "wr_scene_info_get", "wr_scene
            "wr_film_write_image", "wr_checkpoint_save", "wr_checkpoint_load", "wr_last_error", "wr_api_version",
            "wr_reserve", "wr_request_hw_queues", "wr_render_bdpt_moments", "wr_render_vcm_moments",
            "wr_render_path_moments", "wr_film_error", "wr_render_features", "wr_film_denoise",
-           "wr_camera_rays", "wr_trace_closest_dev", "wr_occluded_dev", "wr_path_radiance_dev"]
+           "wr_camera_rays", "wr_trace_closest_dev", "wr_occluded_dev", "wr_path_radiance_dev",
+           "wr_bsdf_eval_dev", "wr_bsdf_sample_dev", "wr_light_illuminate_dev", "wr_light_emit_dev",
+           "wr_light_radiance_dev", "wr_rng_uniform_dev"]
 CKPT_BDPT, CKPT_VCM, CKPT_PT = 1, 2, 3
 FILM_PT, FILM_BDPT = 0, 1
 
@@ -218,6 +220,13 @@ def lib():
         L.wr_trace_closest_dev.argtypes = [P, P, I64, P]
         L.wr_occluded_dev.argtypes = [P, P, P, I64, P]
         L.wr_path_radiance_dev.argtypes = [P, P, I64, I, C.c_uint32, I, P, P, C.POINTER(WrStats)]
+        U32 = C.c_uint32
+        L.wr_bsdf_eval_dev.argtypes = [P, P, P, P, I64, P, P]
+        L.wr_bsdf_sample_dev.argtypes = [P, P, P, P, I64, P, P]
+        L.wr_light_illuminate_dev.argtypes = [P, P, P, P, I64, P]
+        L.wr_light_emit_dev.argtypes = [P, P, P, P, I64, P]
+        L.wr_light_radiance_dev.argtypes = [P, P, P, I64, P]
+        L.wr_rng_uniform_dev.argtypes = [P, U32, U32, U32, P, P, C.c_int32, I64, P]
         L.wr_last_error.restype = C.c_char_p
         _lib = L
     return _lib
@@ -376,6 +385,58 @@ def hit_fields(hits):
     f32 = np.float32 if isinstance(hits, np.ndarray) else sys.modules["torch"].float32
     return {"t": hits[:, 0].view(f32), "p": hits[:, 1:4].view(f32), "n": hits[:, 4:7].view(f32),
             "prim": hits[:, 7], "inside": hits[:, 8], "mat_id": hits[:, 9]}
+
+
+def _record_fields(rec, words, name, layout):
+    """Views of the columns of (n, words) int32 records (a torch tensor or a
+    numpy array): layout = (field, first word, last word + 1, is float)."""
+    if rec.ndim != 2 or rec.shape[1] != words:
+        raise ValueError(f"{name} must have shape (n, {words}), got {tuple(rec.shape)}")
+    f32 = np.float32 if isinstance(rec, np.ndarray) else sys.modules["torch"].float32
+    out = {}
+    for field, lo, hi, is_float in layout:
+        col = rec[:, lo] if hi == lo + 1 else rec[:, lo:hi]
+        out[field] = col.view(f32) if is_float else col
+    return out
+
+
+def bsdf_info_fields(info):
+    """(n, 9) int32 wr_bsdf_info records: valid, is_delta (n,) int32; cos_wi,
+    continue_prob, fresnel (n,) and prob (n, 4: diffuse, glossy, reflect, refract) float32."""
+    return _record_fields(info, 9, "info", (("valid", 0, 1, False), ("is_delta", 1, 2, False), ("cos_wi", 2, 3, True),
+                                            ("continue_prob", 3, 4, True), ("fresnel", 4, 5, True),
+                                            ("prob", 5, 9, True)))
+
+
+def bsdf_eval_fields(ev):
+    """(n, 8) int32 wr_bsdf_eval records: f (n, 3); cos_wo, dir_pdf, rev_pdf, pdf, pdf_rev (n,) float32."""
+    return _record_fields(ev, 8, "eval", (("f", 0, 3, True), ("cos_wo", 3, 4, True), ("dir_pdf", 4, 5, True),
+                                          ("rev_pdf", 5, 6, True), ("pdf", 6, 7, True), ("pdf_rev", 7, 8, True)))
+
+
+def bsdf_sample_fields(smp):
+    """(n, 9) int32 wr_bsdf_sample records: f, wo (n, 3), pdf, cos_wo (n,) float32; type (n,) int32."""
+    return _record_fields(smp, 9, "sample", (("f", 0, 3, True), ("wo", 3, 6, True), ("pdf", 6, 7, True),
+                                             ("cos_wo", 7, 8, True), ("type", 8, 9, False)))
+
+
+_LIGHT_LAYOUTS = {
+    10: (("le", 0, 3, True), ("dir", 3, 6, True), ("dist", 6, 7, True), ("direct_pdf", 7, 8, True),
+         ("emission_pdf", 8, 9, True), ("cos_light", 9, 10, True)),
+    12: (("le_cos", 0, 3, True), ("pos", 3, 6, True), ("dir", 6, 9, True), ("emission_pdf", 9, 10, True),
+         ("direct_pdf_a", 10, 11, True), ("cos_light", 11, 12, True)),
+    5: (("le", 0, 3, True), ("direct_pdf_a", 3, 4, True), ("emission_pdf", 4, 5, True)),
+}
+
+
+def light_fields(rec):
+    """The float32 columns of the light calls' records, told apart by their
+    width: (n, 10) wr_light_illum (le, dir, dist, direct_pdf, emission_pdf,
+    cos_light), (n, 12) wr_light_emission (le_cos, pos, dir, emission_pdf,
+    direct_pdf_a, cos_light), (n, 5) wr_light_rad (le, direct_pdf_a, emission_pdf)."""
+    if rec.ndim != 2 or rec.shape[1] not in _LIGHT_LAYOUTS:
+        raise ValueError(f"light records must have shape (n, 10), (n, 12) or (n, 5), got {tuple(rec.shape)}")
+    return _record_fields(rec, rec.shape[1], "light records", _LIGHT_LAYOUTS[rec.shape[1]])
 
 
 def rays_from_arrays(o, d, tmin=0.0, tmax=1e7):
@@ -558,6 +619,99 @@ class Context:
                                          C.c_void_p(rgb.data_ptr()),
                                          C.c_void_p(rgb_sq.data_ptr()) if rgb_sq is not None else None, C.byref(st)))
         return rgb, st
+
+    # ---- shading on device arrays (wr_bsdf_*_dev, wr_light_*_dev, wr_rng_uniform_dev;
+    # DESIGN.md 13).  Tensors and streams as the _t calls above.  Records come
+    # back as (n, words) int32 tensors, like trace_closest_t's hits; the
+    # *_fields functions name their columns.
+    def _shade_call(self, fn, n, inputs, outputs):
+        """inputs / outputs: (tensor, name, shape, dtype); an output that is None
+        is made here.  Calls fn(ctx, inputs..., n, outputs...) and returns the outputs."""
+        import torch
+        for spec in inputs:
+            _dev_tensor(*spec, None)
+        outs = [(torch.empty(shape, dtype=getattr(torch, dtype), device=inputs[0][0].device) if t is None else t,
+                 name, shape, dtype) for t, name, shape, dtype in outputs]
+        self._dev_args(*inputs, *outs)
+        check(fn(self.h, *[C.c_void_p(a[0].data_ptr()) for a in inputs], n,
+                 *[C.c_void_p(a[0].data_ptr()) for a in outs]))
+        return [a[0] for a in outs]
+
+    def bsdf_eval_t(self, hits, wi, wo, info=None, out=None):
+        """wr_bsdf_eval_dev: hits (n, 10) int32 as trace_closest_t returns them,
+        wi and wo (n, 3) float32 (wi = -ray.d).  Returns (info, eval): int32
+        (n, 9) wr_bsdf_info and (n, 8) wr_bsdf_eval records (`info` / `out`
+        when given, written in place); bsdf_info_fields / bsdf_eval_fields name
+        the columns."""
+        _dev_tensor(hits, "hits", (None, 10), "int32", None)
+        n = hits.shape[0]
+        return tuple(self._shade_call(
+            lib().wr_bsdf_eval_dev, n,
+            [(hits, "hits", (n, 10), "int32"), (wi, "wi", (n, 3), "float32"), (wo, "wo", (n, 3), "float32")],
+            [(info, "info", (n, 9), "int32"), (out, "out", (n, 8), "int32")]))
+
+    def bsdf_sample_t(self, hits, wi, r3, info=None, out=None):
+        """wr_bsdf_sample_dev: as bsdf_eval_t with r3 (n, 3) float32 uniform
+        draws in place of wo.  Returns (info, sample): (n, 9) wr_bsdf_info and
+        (n, 9) wr_bsdf_sample records (bsdf_sample_fields)."""
+        _dev_tensor(hits, "hits", (None, 10), "int32", None)
+        n = hits.shape[0]
+        return tuple(self._shade_call(
+            lib().wr_bsdf_sample_dev, n,
+            [(hits, "hits", (n, 10), "int32"), (wi, "wi", (n, 3), "float32"), (r3, "r3", (n, 3), "float32")],
+            [(info, "info", (n, 9), "int32"), (out, "out", (n, 9), "int32")]))
+
+    def light_illuminate_t(self, light, pos, r3, out=None):
+        """wr_light_illuminate_dev: light (n,) int32 indices, pos and r3 (n, 3)
+        float32.  Returns (n, 10) int32 wr_light_illum records (light_fields)."""
+        _dev_tensor(light, "light", (None,), "int32", None)
+        n = light.shape[0]
+        return self._shade_call(
+            lib().wr_light_illuminate_dev, n,
+            [(light, "light", (n,), "int32"), (pos, "pos", (n, 3), "float32"), (r3, "r3", (n, 3), "float32")],
+            [(out, "out", (n, 10), "int32")])[0]
+
+    def light_emit_t(self, light, dir_r3, pos_r3, out=None):
+        """wr_light_emit_dev: light (n,) int32, dir_r3 and pos_r3 (n, 3) float32
+        uniform draws.  Returns (n, 12) int32 wr_light_emission records (light_fields)."""
+        _dev_tensor(light, "light", (None,), "int32", None)
+        n = light.shape[0]
+        return self._shade_call(
+            lib().wr_light_emit_dev, n,
+            [(light, "light", (n,), "int32"), (dir_r3, "dir_r3", (n, 3), "float32"),
+             (pos_r3, "pos_r3", (n, 3), "float32")],
+            [(out, "out", (n, 12), "int32")])[0]
+
+    def light_radiance_t(self, hits, ray_d, out=None):
+        """wr_light_radiance_dev: hits (n, 10) int32, ray_d (n, 3) float32 (the
+        direction of the ray that hit).  Returns (n, 5) int32 wr_light_rad
+        records (light_fields): zeros unless the hit is on a light."""
+        _dev_tensor(hits, "hits", (None, 10), "int32", None)
+        n = hits.shape[0]
+        return self._shade_call(
+            lib().wr_light_radiance_dev, n,
+            [(hits, "hits", (n, 10), "int32"), (ray_d, "ray_d", (n, 3), "float32")],
+            [(out, "out", (n, 5), "int32")])[0]
+
+    def rng_uniform_t(self, n, draws, seed, iteration, subpath, path=None, ctr=None, out=None):
+        """wr_rng_uniform_dev: (n, draws) float32 draws of the counter RNG,
+        stream (seed, iteration, subpath, path[k]) for row k (path: (n,) int32
+        holding the uint32 values, or None for path k = k).  ctr: (n,) int32
+        counters, read and advanced in place (None: every stream from its
+        first draw, nothing kept)."""
+        if not isinstance(n, int) or not isinstance(draws, int) or n < 0 or not 1 <= draws <= 64:
+            raise ValueError(f"n must be an int >= 0 and draws an int in 1..64, got {n!r}, {draws!r}")
+        import torch
+        specs = [(t, name, (n,), "int32") for t, name in ((path, "path"), (ctr, "ctr")) if t is not None]
+        for spec in specs:
+            _dev_tensor(*spec, None)
+        if out is None:
+            dev = specs[0][0].device if specs else f"cuda:{self.devices()[0]}"
+            out = torch.empty((n, draws), dtype=torch.float32, device=dev)
+        self._dev_args(*specs, (out, "out", (n, draws), "float32"))
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        check(lib().wr_rng_uniform_dev(self.h, seed, iteration, subpath, ptr(path), ptr(ctr), draws, n, ptr(out)))
+        return out
 
     def render_bdpt(self, width, height, iterations=1, seed=5489, iter_begin=0, control_length=3,
                     max_path_length=10, faithful=1, time_kernels=0, count_work=0, film=None, film_ptr=None):
