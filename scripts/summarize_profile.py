@@ -120,7 +120,9 @@ def main():
                 if any(short(r["Name"]).startswith(f + "<false") for f in fam)]
         calls = sum(int(r["Calls"]) for r in rows if short(r["Name"]).startswith(lead + "<false"))
         tot = sum(float(r["TotalDurationNs"]) for r in rows)
-        r = line["roofline"]
+        r = line.get("roofline")
+        if not r:  # a plain run's line (no --full): nothing to compare the durations with
+            return
         cmp_ = {"rocprof_kernels": [short(r_["Name"]) for r_ in rows],
                 "rocprof_steps": calls, "rocprof_avg_ms_per_step": round(tot / max(1, calls) / 1e6, 4),
                 "bench_launches": r["launches"], "bench_event_avg_ms": r["avg_launch_ms"],

@@ -508,10 +508,10 @@ __device__ __forceinline__ void queue_connection(const BdptArgs& A, int qslot, b
 // (vertex_inputs): everything whose address follows from the path and the
 // primitive -- the primitive's records, the path's state record and the other
 // pass's vertex count -- issued as one straight-line block before any of it
-// is used.  A lane without work (no queue entry, a miss, a pending hard ray)
-// reads record 0 and drops it, so no branch guards a load.
+// is used.  A lane without work (a spare lane of the hit list's last wave)
+// reads a valid record and drops it, so no branch guards a load.
 struct VtxIn {
-  int p, prim;  // p = -1: the lane has no queue entry
+  int p, prim;  // p = -1: the lane has no entry of the hit list
   float t;
   V3 o, d;
   PrimIn g;
@@ -535,8 +535,99 @@ __device__ __forceinline__ VtxIn vertex_inputs(const BdptArgs& A, bool on, int p
   return v;
 }
 
-// One light-subpath vertex (:77-128): path p's ray (o, d) hit prim at t
-// (prim < 0: a miss -- nothing to do).  Every lane of the wave calls it
+// Hit compaction.  A vertex kernel shades only the queue entries whose ray hit
+// something (prim >= 0), in full waves: a missed entry has no vertex, and a
+// lane that carries one idles through the whole vertex of its wave.  A block
+// takes a chunk of kShadeBlock x R consecutive entries (R: hit_chunk_r, uniform
+// per launch), reads their q_prim column -- R independent coalesced loads per
+// thread -- and lists in LDS, in queue order, the chunk offsets of the entries
+// that hit: a ballot per 64-entry segment, the segment counts through LDS.
+// The block then runs stage A and the vertex over the list, kShadeBlock entries
+// per round; only the list's last wave is partial.
+constexpr int kHitR = 4;  // entries per thread and chunk, at most
+constexpr int kHitSegs = kHitR * (kShadeBlock / 64);
+static_assert(kShadeBlock * kHitR <= 65536 && kHitSegs % 4 == 0, "16-bit offsets; counts read as int4");
+struct HitList {
+  alignas(16) int seg[kHitSegs];       // hits per segment; segment r * (kShadeBlock / 64) + wave
+  uint16_t at[kShadeBlock * kHitR];    // chunk offsets of the entries that hit, in queue order
+};
+// R of a launch over n entries by nblk blocks: 1 while the launch has a block
+// per kShadeBlock entries (a small launch spreads over as many blocks as
+// before), up to kHitR where the blocks loop anyway
+__device__ __forceinline__ int hit_chunk_r(int n, int nblk) {
+  const int lanes = nblk * kShadeBlock;
+  int r = 1;
+#pragma unroll
+  for (int k = 1; k < kHitR; ++k) r += n > k * lanes ? 1 : 0;  // min(kHitR, ceil(n / lanes)) without the division
+  return r;
+}
+// Lists the hits among entries [e0, e0 + cn) of the queue (cn <= kShadeBlock *
+// R) and returns their number.  Every thread of the block calls it (two
+// barriers); the list stays valid until the block's next call.  The barriers
+// order the reuse: seg is read only between them, and `at` is written only
+// after the first, which no wave passes before every wave has left the
+// previous chunk's rounds.
+// LIGHT: a missed entry ends its light subpath (:81-82), so its path's lvc
+// byte loses kLightAlive here -- q_path, then the byte.  (The byte's low bits
+// are always the stored-vertex count, so the state record is not read; the
+// thread owns the path for the launch.)
+template <bool LIGHT>
+__device__ __forceinline__ int compact_hits(HitList& L, const int* q_prim, const int* q_path, uint8_t* lvc, int tid,
+                                            int e0, int cn, int R) {
+  const int lane = tid & 63, w = tid >> 6;
+  constexpr int kW = kShadeBlock / 64;
+  int prim[kHitR], mp[kHitR];  // mp: the path of a missed entry (LIGHT), else -1
+  bool in[kHitR];
+  unsigned long long m[kHitR];
+#pragma unroll
+  for (int r = 0; r < kHitR; ++r) {
+    const int k = r * kShadeBlock + tid;
+    in[r] = r < R && k < cn;
+    prim[r] = in[r] ? q_prim[e0 + k] : -1;
+  }
+#pragma unroll
+  for (int r = 0; r < kHitR; ++r) {
+    m[r] = __ballot(prim[r] >= 0);
+    if (lane == 0) L.seg[r * kW + w] = __popcll(m[r]);  // (0 for r >= R)
+    mp[r] = (LIGHT && in[r] && prim[r] < 0) ? q_path[e0 + r * kShadeBlock + tid] : -1;
+  }
+  __syncthreads();
+  int cnt[kHitSegs];
+#pragma unroll
+  for (int i = 0; i < kHitSegs / 4; ++i) {
+    const int4 v = reinterpret_cast<const int4*>(L.seg)[i];
+    cnt[4 * i] = v.x;
+    cnt[4 * i + 1] = v.y;
+    cnt[4 * i + 2] = v.z;
+    cnt[4 * i + 3] = v.w;
+  }
+  int mb[kHitR];
+  if (LIGHT) {
+#pragma unroll
+    for (int r = 0; r < kHitR; ++r) mb[r] = mp[r] >= 0 ? lvc[mp[r]] : 0;
+  }
+  int base[kHitR], total = 0;
+#pragma unroll
+  for (int i = 0; i < kHitSegs; ++i) {
+    if ((i % kW) == w) base[i / kW] = total;
+    total += cnt[i];
+  }
+#pragma unroll
+  for (int r = 0; r < kHitR; ++r)
+    if (prim[r] >= 0)
+      L.at[base[r] + __popcll(m[r] & ((1ull << lane) - 1ull))] = static_cast<uint16_t>(r * kShadeBlock + tid);
+  if (LIGHT) {
+#pragma unroll
+    for (int r = 0; r < kHitR; ++r)
+      if (mp[r] >= 0) lvc[mp[r]] = static_cast<uint8_t>(mb[r] & ~kLightAlive);
+  }
+  __syncthreads();
+  return total;
+}
+
+// One light-subpath vertex (:77-128): path p's ray (o, d) hit prim at t.  A
+// missed entry never comes here (compact_hits ends its subpath); prim < 0 is
+// a spare lane of the list's last wave.  Every lane of the wave calls it
 // (queue appends).  oslot: the step whose queue gets the extension ray
 // (slot + 1).
 __device__ __forceinline__ void light_vertex(const BdptArgs& A, const DMat* mats, const VtxIn& in, int oslot) {
@@ -647,10 +738,6 @@ __device__ __forceinline__ void light_vertex(const BdptArgs& A, const DMat* mats
     } else {  // an invalid BSDF ends the subpath (:86-88)
       B.lvc[p] = static_cast<uint8_t>(bq_count(pk));
     }
-  } else if (p >= 0) {  // a miss ends the subpath (:81-82)
-    // (lvc's low bits are always the state record's stored-vertex count, so
-    // clearing kLightAlive needs no read of the byte)
-    B.lvc[p] = static_cast<uint8_t>(bq_count(pk));
   }
   const int ei = wave_append(&A.sc->ext[oslot], ext);
   if (ext) {
@@ -709,21 +796,29 @@ __global__ void __launch_bounds__(kShadeBlock) WR_SHADE_OCC k_light_shade(BdptGr
   const int cur = slot & 1;
   const int n = A.sc->ext[slot];
   if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&A.ctr->closest, (unsigned long long)n);
-  const int gstride = gridDim.x * blockDim.x;
-  const int nround = (n + gstride - 1) / gstride * gstride;  // whole waves reach the appends
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < nround; j += gstride) {
-    // stage A: the entry's columns, all at once (a lane past the end reads the
-    // last entry; n > 0 here)
-    const int e = min(j, n - 1);
-    const int p = B.q_path[cur][e], prim = B.q_prim[cur][e];
-    const float t = B.q_t[cur][e];
-    const V3 o = ld3(B.q_o[cur], B.qs, e), d = ld3(B.q_d[cur], B.qs, e);
+  __shared__ HitList s_hits;
+  const int R = hit_chunk_r(n, gridDim.x), chunk = R * kShadeBlock;
+  // (i: the thread's index, then its place in the list -- the thread index
+  // again modulo kShadeBlock, so the vertex keeps one lane counter)
+  int i = threadIdx.x;
+  for (int c0 = blockIdx.x * chunk; c0 < n; c0 += gridDim.x * chunk) {  // (block-uniform: every thread reaches the barriers)
+    i &= kShadeBlock - 1;
+    const int nh = compact_hits<true>(s_hits, B.q_prim[cur], B.q_path[cur], B.lvc, i, c0, min(chunk, n - c0), R);
+    // whole waves reach the appends: the list's last wave runs with its spare lanes off
+    for (; (i & ~63) < nh; i += kShadeBlock) {
+      // stage A: the entry's columns, all at once (a spare lane reads the
+      // list's last entry)
+      const int e = c0 + s_hits.at[min(i, nh - 1)];
+      const int p = B.q_path[cur][e], prim = B.q_prim[cur][e];
+      const float t = B.q_t[cur][e];
+      const V3 o = ld3(B.q_o[cur], B.qs, e), d = ld3(B.q_d[cur], B.qs, e);
 #ifdef WR_DEBUG_PATH
-    if (j < n && A.base + p == WR_DEBUG_PATH && A.iter == WR_DEBUG_ITER)
-      printf("[dbg gpu] light step %d ray o %a %a %a d %a %a %a prim %d t %a\n", slot, o.x, o.y, o.z, d.x, d.y, d.z, prim,
-             t);
+      if (i < nh && A.base + p == WR_DEBUG_PATH && A.iter == WR_DEBUG_ITER)
+        printf("[dbg gpu] light step %d ray o %a %a %a d %a %a %a prim %d t %a\n", slot, o.x, o.y, o.z, d.x, d.y, d.z,
+               prim, t);
 #endif
-    light_vertex(A, mats, vertex_inputs<false>(A, j < n, p, prim, t, o, d), slot + 1);
+      light_vertex(A, mats, vertex_inputs<false>(A, i < nh, p, prim, t, o, d), slot + 1);
+    }
   }
 }
 
@@ -790,7 +885,8 @@ __global__ void __launch_bounds__(kShadeBlock) WR_NO_PK_FP32 k_camera_gen(BdptGr
 
 // One camera-subpath vertex (:148-260): emitter hit, DI setup, vertex
 // connections (shadow rays queued), scattering -- path p's ray (o, d) hit prim
-// at t (prim < 0: a miss: nothing).  Every lane of the wave calls it.  oslot:
+// at t (prim < 0: a spare lane of the hit list's last wave; a missed entry is
+// never listed, compact_hits).  Every lane of the wave calls it.  oslot:
 // the step whose queues (shadow / aux, DI records, extension) get this
 // vertex's rays (slot + 1).
 // ebase: the queue index of the camera pass's first extension ray of step
@@ -1008,16 +1104,23 @@ __device__ __forceinline__ void camera_shade_body(const BdptArgs& A, const DMat*
   const int cur = slot & 1;
   const int n = A.sc->ext[slot], e0 = cam_ext_base(A, slot), eb = cam_ext_base(A, slot + 1);
   if (bid == 0 && threadIdx.x == 0) atomicAdd(&A.ctr->closest, (unsigned long long)n);
-  const int gstride = nblk * blockDim.x;
-  const int nround = (n + gstride - 1) / gstride * gstride;
-  for (int j = bid * blockDim.x + threadIdx.x; j < nround; j += gstride) {
-    // stage A: the entry's columns, all at once (a lane past the end reads the
-    // last entry; n > 0 here)
-    const int e = e0 + min(j, n - 1);
-    const int p = B.q_path[cur][e], prim = B.q_prim[cur][e];
-    const float t = B.q_t[cur][e];
-    const V3 o = ld3(B.q_o[cur], B.qs, e), d = ld3(B.q_d[cur], B.qs, e);
-    camera_vertex(A, mats, lights, vertex_inputs<true>(A, j < n, p, prim, t, o, d), slot + 1, eb);
+  // the hit entries of each chunk, in full waves (compact_hits; a missed
+  // camera ray needs nothing)
+  __shared__ HitList s_hits;
+  const int R = hit_chunk_r(n, nblk), chunk = R * kShadeBlock, e1 = e0 + n;
+  int i = threadIdx.x;  // (the thread's index, then its place in the list: k_light_shade)
+  for (int c0 = e0 + bid * chunk; c0 < e1; c0 += nblk * chunk) {  // (block-uniform: every thread reaches the barriers)
+    i &= kShadeBlock - 1;
+    const int nh = compact_hits<false>(s_hits, B.q_prim[cur], nullptr, nullptr, i, c0, min(chunk, e1 - c0), R);
+    for (; (i & ~63) < nh; i += kShadeBlock) {
+      // stage A: the entry's columns, all at once (a spare lane of the list's
+      // last wave reads the last entry)
+      const int e = c0 + s_hits.at[min(i, nh - 1)];
+      const int p = B.q_path[cur][e], prim = B.q_prim[cur][e];
+      const float t = B.q_t[cur][e];
+      const V3 o = ld3(B.q_o[cur], B.qs, e), d = ld3(B.q_d[cur], B.qs, e);
+      camera_vertex(A, mats, lights, vertex_inputs<true>(A, i < nh, p, prim, t, o, d), slot + 1, eb);
+    }
   }
 }
 
