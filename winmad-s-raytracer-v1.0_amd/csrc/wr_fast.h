@@ -81,6 +81,10 @@ struct FastCounters {  // algorithmic work (count_work)
   // kd_walk_wave (count_work): walks, their rounds and nodes, and fall-backs
   // to the serial walk (work stack or hit list outgrown)
   uint32_t ww_walks, ww_rounds, ww_nodes, ww_over;
+  // the search's outer rounds (count_work; per wave: every lane counts alike),
+  // those in which a lane finished its ray, the finishing lanes (per lane), and
+  // the full 64-ray settle batches (RL, per wave)
+  uint32_t rounds, fin_rounds, fin_lanes, settle_full;
 };
 
 // Per wave: the stack columns, 8 bytes per entry and lane (BVH: link + entry t;
@@ -126,7 +130,7 @@ __host__ __device__ constexpr size_t search_lds_bytes(int depth, int wide) {
   return size_t(depth < search_lds_stack(wide) ? depth : search_lds_stack(wide)) * 64 * 6;
 }
 // The search's workgroup: WG waves, and in its dynamic LDS
-//   [top set: nodes [0, ntop) of the search tree][stack columns + RL list buffer] x WG
+//   [top set: nodes [0, ntop) of the search tree][stack columns + RL list and settle buffers] x WG
 // The top set is the parent-closed head of the node array (wrf::build_fast's
 // top-first order): every wave copies its share in, one barrier, and a lane
 // whose node index is below ntop reads the same 64 (4-wide: 128) bytes with
@@ -139,8 +143,12 @@ __host__ __device__ constexpr size_t search_node_bytes(int wide) {
 // node against bank conflicts, alike; a "top phase" in which only lanes inside
 // the top set step while there is one, -25 % on C2.)
 __host__ __device__ constexpr size_t search_top_bytes(int ntop, int wide) { return size_t(ntop) * search_node_bytes(wide); }
+// RL, behind the stack columns: the list buffer (64 launch indices) and the
+// settle buffer (kSettleCap finished unmarked hits, launch index + winner)
+constexpr int kSettleCap = 128;
+__host__ __device__ constexpr size_t search_rl_bytes() { return 64 * sizeof(int) + kSettleCap * 2 * sizeof(int); }
 __host__ __device__ constexpr size_t search_wave_bytes(int depth, int wide, bool rl) {
-  return search_lds_bytes(depth, wide) + (rl ? 64 * sizeof(int) : 0);
+  return search_lds_bytes(depth, wide) + (rl ? search_rl_bytes() : 0);
 }
 __host__ __device__ constexpr size_t search_wg_bytes(int depth, int wide, bool rl, int ntop, int wg) {
   return search_top_bytes(ntop, wide) + size_t(wg) * search_wave_bytes(depth, wide, rl);
@@ -1443,12 +1451,17 @@ __device__ __forceinline__ int fast_append(int* counter, bool want) {
 // The resolve's first membership test (resolve_fast): is one of the first
 // four KD leaf cells of the winner p1 (its PrimRec) crossed by the ray within
 // the witness margin?  Then the reference's walk visits a leaf holding p1.
+// The record is read in two halves, the second only by the lanes the first
+// two cells do not prove (the search's settle batches: half the uncoalesced
+// loads for most rays; C2 +1 %, C4 +3 % over one read of all six).
 __device__ __forceinline__ bool first_cells_crossed(const FastScene& F, int p1, V3 o, V3 d, V3 binv, float rtmax) {
   const float4* pr = F.prim_rec + 8 * static_cast<size_t>(p1);
-  const float4 c0 = pr[0], c1 = pr[1], c2 = pr[2], c3 = pr[3], c4 = pr[4], c5 = pr[5];
-  return box_crossed_with_margin(c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, o, d, binv, rtmax) ||
-         box_crossed_with_margin(c1.z, c1.w, c2.x, c2.y, c2.z, c2.w, o, d, binv, rtmax) ||
-         box_crossed_with_margin(c3.x, c3.y, c3.z, c3.w, c4.x, c4.y, o, d, binv, rtmax) ||
+  const float4 c0 = pr[0], c1 = pr[1], c2 = pr[2];
+  if (box_crossed_with_margin(c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, o, d, binv, rtmax) ||
+      box_crossed_with_margin(c1.z, c1.w, c2.x, c2.y, c2.z, c2.w, o, d, binv, rtmax))
+    return true;
+  const float4 c3 = pr[3], c4 = pr[4], c5 = pr[5];
+  return box_crossed_with_margin(c3.x, c3.y, c3.z, c3.w, c4.x, c4.y, o, d, binv, rtmax) ||
          box_crossed_with_margin(c4.z, c4.w, c5.x, c5.y, c5.z, c5.w, o, d, binv, rtmax);
 }
 
@@ -1456,7 +1469,8 @@ __device__ __forceinline__ bool first_cells_crossed(const FastScene& F, int p1, 
 // or an unmarked winner that first_cells_crossed proves -- is settled here;
 // the others (near-ties, grazing rays, winners proven by neither of those
 // cells) are listed by launch index in rlist for k_fast_resolve, which then
-// reads those rays only.  The test is the resolve's own, on the same floats.
+// reads those rays only.  The test is the resolve's own, on the same floats,
+// and runs in full waves over the settle buffer (settle_batch below).
 template <bool COUNT, int W, bool SPH, bool RL = false>
 __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F, const TraceQueues& Q, int* fetch,
                                            float* t2buf, int2* pairs, int2* spill, uint32_t* smem, FastCounters& ctr,
@@ -1531,6 +1545,55 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
     if (lane < nlb) rlist[base + lane] = lbuf[lane];
     nlb = 0;
   };
+  // (wave-uniform) the lanes with `want` append their launch index to lbuf
+  auto list_append = [&](bool want, int idx) {
+    const unsigned long long m = __ballot(want);
+    if (m == 0ull) return;
+    const int k = __popcll(m);
+    if (nlb + k > 64) flush_list();
+    if (want) lbuf[nlb + __popcll(m & ((1ull << lane) - 1ull))] = idx;
+    nlb += k;
+  };
+  // RL, the settle buffer: a finished ray with an unmarked winner is proven (or
+  // listed) by first_cells_crossed, the resolve's first membership test -- six
+  // uncoalesced loads that depend on p1.  Run by the finishing lanes alone it
+  // would put that round trip on every outer round's chain with most lanes
+  // off; instead the lane leaves (launch index, p1) here and refills, and the
+  // wave runs the test over 64 entries at a time, every lane on, the ray's o,
+  // d, tmax read again beside p1's record in one round trip (settle_batch).
+  // At most 63 entries stay behind a batch and a round adds at most 64.
+  int2* const sbuf = reinterpret_cast<int2*>(lbuf + 64);
+  int nsb = 0;
+  bool queued = false;
+  auto settle_batch = [&]() {  // (wave-uniform) the first min(nsb, 64) entries
+    const int m = min(nsb, 64);
+    if (COUNT && m == 64) ++ctr.settle_full;
+    bool unproven = false;
+    int sidx = 0;
+    if (lane < m) {
+      const int2 e = sbuf[lane];
+      sidx = e.x;
+      int sq = 0, sr = 0;
+      QI.locate(sidx, sq, sr);
+      const float* o3 = qfield(Q, sq, [](const RayQueue& x) { return x.o3; });
+      const float* d3 = qfield(Q, sq, [](const RayQueue& x) { return x.d3; });
+      const int cap = qfield(Q, sq, [](const RayQueue& x) { return x.cap; });
+      const float* tmx = qfield(Q, sq, [](const RayQueue& x) { return x.tmax; });
+      const V3 so = v3(o3[sr], o3[cap + sr], o3[2 * cap + sr]);
+      const V3 sd = v3(d3[sr], d3[cap + sr], d3[2 * cap + sr]);
+      const float stmax = tmx ? tmx[sr] : WR_INF;
+      const V3 sbinv = v3(clamp_inv(sd.x), clamp_inv(sd.y), clamp_inv(sd.z));
+      unproven = !first_cells_crossed(F, e.y, so, sd, sbinv, stmax);
+    }
+    list_append(unproven, sidx);
+    const int rest = nsb - m;  // < 64: the tail moves down
+    if (rest > 0) {
+      int2 e = make_int2(0, 0);
+      if (lane < rest) e = sbuf[64 + lane];
+      if (lane < rest) sbuf[lane] = e;
+    }
+    nsb = rest;
+  };
   auto reserve = [&](bool want) -> int {
     const unsigned long long m = __ballot(want);
     const int need = __popcll(m);
@@ -1602,6 +1665,10 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
     }
   };
   for (;;) {
+    // ---- RL: a full wave of finished rays to settle
+    if constexpr (RL) {
+      if (nsb >= 64) settle_batch();
+    }
     // ---- refill idle lanes
     if (pool) {
       const bool idle = r < 0;
@@ -1925,8 +1992,13 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
 #endif
     }
     // ---- finished rays: the candidate goes to k_fast_resolve
+    if (COUNT) {
+      ++ctr.rounds;
+      if (__ballot(act && cur == kDone && pl >= 0)) ++ctr.fin_rounds;
+    }
     if (act && cur == kDone && pl >= 0) {
       if (COUNT) {
+        ++ctr.fin_lanes;
         ctr.max_nodes = max(ctr.max_nodes, rn);
         ctr.max_tests = max(ctr.max_tests, rt);
         ctr.long_rays += rn > 256u ? 1u : 0u;
@@ -1951,23 +2023,26 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
       qfield(Q, qi, [](const RayQueue& x) { return x.out_t; })[r] = p1 >= 0 ? t1 : WR_INF;
       qfield(Q, qi, [](const RayQueue& x) { return x.out_prim; })[r] = po;
       if constexpr (RL) {
-        listed = po != p1;  // marked: a near-tie or a grazing ray
-        if (!listed && p1 >= 0) listed = !first_cells_crossed(F, p1, o, d, binv, rtmax);
+        listed = po != p1;             // marked: a near-tie or a grazing ray
+        queued = !listed && p1 >= 0;   // an unmarked hit: the settle buffer (a miss is settled)
       }
       r = -1;
     }
-    if constexpr (RL) {  // (wave-uniform) the listed rays into the wave's buffer
-      const unsigned long long m = __ballot(listed);
+    if constexpr (RL) {  // (wave-uniform) the listed rays into the wave's buffer, the unmarked hits into the settle buffer
+      list_append(listed, lidx);
+      listed = false;
+      const unsigned long long m = __ballot(queued);
       if (m) {
-        const int k = __popcll(m);
-        if (nlb + k > 64) flush_list();
-        if (listed) lbuf[nlb + __popcll(m & ((1ull << lane) - 1ull))] = lidx;
-        nlb += k;
-        listed = false;
+        if (queued) sbuf[nsb + __popcll(m & ((1ull << lane) - 1ull))] = make_int2(lidx, p1);
+        nsb += __popcll(m);
+        queued = false;
       }
     }
   }
-  if constexpr (RL) flush_list();
+  if constexpr (RL) {
+    while (nsb > 0) settle_batch();  // the remainder: at most a full and a partial batch
+    flush_list();
+  }
 }
 
 // tie-list entries: launch index, | kWalkEntry for a ray the KD walk settles,

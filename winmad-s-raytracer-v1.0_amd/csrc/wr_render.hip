@@ -158,6 +158,7 @@ struct DevCounters {
   unsigned long long verify_rays, verify_bad;                   // WR_BVH_VERIFY
   unsigned long long lat[12];  // WR_TRACE_BVH latency tail (FastCounters mem_max .. scans; max or sum; tie_col .. tie_pass2)
   unsigned long long ww[4];   // kd_walk_wave: walks, rounds, nodes, serial fall-backs
+  unsigned long long rounds[4];  // the search (count_work): outer rounds, rounds with a finisher, finishing lanes, full settle batches
   unsigned long long overflow;  // BDPT: appends a full vertex pool / shadow queue dropped (the render is redone)
 };
 
@@ -294,6 +295,13 @@ __device__ __forceinline__ void fast_counts(DevCounters* ctr, const FastCounters
     const uint32_t ww[4] = {fc.ww_walks, fc.ww_rounds, fc.ww_nodes, fc.ww_over};
     for (int k = 0; k < 4; ++k)
       if (ww[k]) atomicAdd(&ctr->ww[k], static_cast<unsigned long long>(ww[k]));
+  }
+  const unsigned long long fin = wave_sum(fc.fin_lanes);
+  if (lane_id() == 0 && fc.rounds) {  // (the rounds and batches are the wave's: every lane counted alike)
+    atomicAdd(&ctr->rounds[0], static_cast<unsigned long long>(fc.rounds));
+    atomicAdd(&ctr->rounds[1], static_cast<unsigned long long>(fc.fin_rounds));
+    atomicAdd(&ctr->rounds[2], fin);
+    atomicAdd(&ctr->rounds[3], static_cast<unsigned long long>(fc.settle_full));
   }
 }
 #ifndef WR_FAST_WAVES
@@ -1344,6 +1352,15 @@ int ensure_t2(wr_context* c, Pipe& p, size_t rays) {
 
 // One persistent traversal launch over the queues of Q (max_rays bounds the
 // grid).  WR_TRACE_BVH: the verified-BVH search + its resolve launch instead.
+// WR_TRACE_LOG, counting launches: the search's outer rounds (DevCounters::rounds)
+static void log_rounds(const unsigned long long r[4]) {
+  if (r[0])
+    std::fprintf(stderr,
+                 "[wr bvh rounds] %llu outer rounds, %llu with a finisher (%.3f), %llu finishing lanes (%.1f per such round), "
+                 "%llu full settle batches\n",
+                 r[0], r[1], double(r[1]) / r[0], r[2], r[1] ? double(r[2]) / r[1] : 0.0, r[3]);
+}
+
 int trace_launch(wr_context* c, hipStream_t stream, DevCounters* ctr, const TraceSlot& ts, Timer& tm, bool count,
                  const TraceQueues& Q_, int max_rays, int mode = TRACE_PLAIN, bool hard_wave = false) {
   int* fetch = ts.fetch;
@@ -1673,12 +1690,14 @@ int finish_render(wr_context* c, int n, wr_stats* st, double t0_host, unsigned l
                    lat[7] * 0.01, lat[8] * 0.01, lat[9], lat[11], lat[10] * 0.01);
     std::fprintf(stderr, "[wr bvh walks] many-leaf %llu, no visited hit %llu, crowd %llu, band %llu\n", why[0], why[1],
                  why[2], why[3]);
-    unsigned long long ww[4] = {0, 0, 0, 0};
+    unsigned long long ww[4] = {0, 0, 0, 0}, rounds[4] = {0, 0, 0, 0};
     for (int i = 0; i < n; ++i) {
       DevCounters h;
       HIPCHK(hipMemcpy(&h, c->pipes[i].ctr, sizeof h, hipMemcpyDeviceToHost));
       for (int k = 0; k < 4; ++k) ww[k] += h.ww[k];
+      for (int k = 0; k < 4; ++k) rounds[k] += h.rounds[k];
     }
+    log_rounds(rounds);
     std::fprintf(stderr, "[wr bvh wave walks] %llu walks, %.1f rounds and %.1f nodes per walk, %llu serial fall-backs\n",
                  ww[0], ww[0] ? double(ww[1]) / ww[0] : 0.0, ww[0] ? double(ww[2]) / ww[0] : 0.0, ww[3]);
     std::fprintf(stderr, "[wr bvh tail] max nodes/ray %llu, max tests/ray %llu, rays > 256 nodes %llu, ties resolved by visit order %llu\n",
@@ -2101,10 +2120,11 @@ static int upload_bvh(wr_context& c, const wr::Scene& s, const wr::SceneFlat& f,
   if (k.bvh_verify >= 0) c.verify = k.bvh_verify != 0;
   if (c.trace_log)
     std::fprintf(stderr,
-                 "[wr bvh] nodes %zu tris %zu depth %d lds %zu B/wave, ntop %d (4-wide %d) WG %d waves, %zu B LDS/workgroup, "
-                 "%d waves/CU -> grid %d waves; kd grid %d\n",
-                 fh.nodes.size(), fh.tris.size(), fs.sdepth, search_lds_bytes(fs.sdepth, wide), fs.ntop, c.ntop4, wg, wgb,
-                 waves_per_cu, c.fast_blocks, c.trace_blocks);
+                 "[wr bvh] nodes %zu tris %zu depth %d lds %zu B/wave + %zu B list and settle buffers, ntop %d (4-wide %d) "
+                 "WG %d waves, %zu B LDS/workgroup, %d waves/CU -> grid %d waves; kd grid %d\n",
+                 fh.nodes.size(), fh.tris.size(), fs.sdepth, search_lds_bytes(fs.sdepth, wide),
+                 c.resolve_list ? search_rl_bytes() : size_t(0), fs.ntop, c.ntop4, wg, wgb, waves_per_cu, c.fast_blocks,
+                 c.trace_blocks);
   return WR_OK;
 }
 
@@ -2258,7 +2278,8 @@ static int trace_api(wr_context* c, const wr_ray* rays, const float* targets, in
   if (c->fast_on && !c->api_spill.p && max_spill_entries(c) > 0)
     if (int rc = c->api_spill.grow(max_spill_entries(c) * size_t(c->fast_blocks) * 64)) return rc;
   const TraceSlot ts{&c->ctr->fetch, c->api_t2.p, c->api_t2.n / 5, &c->ctr->hard[0], c->api_spill.p, &c->ctr->rlist};
-  trace_launch(c, c->stream, c->ctr, ts, tm, false, ql.Q, ql.max_rays,
+  // (WR_TRACE_LOG: the counting kernels, for the rounds line below)
+  trace_launch(c, c->stream, c->ctr, ts, tm, c->trace_log, ql.Q, ql.max_rays,
                c->api_dense ? TRACE_DENSE : (occ != nullptr ? TRACE_CUT : TRACE_PLAIN), true);
   hipLaunchKernelGGL(k_api_finish, dim3(g), dim3(256), 0, c->stream, c->ds, o3, d3, tt, pr, dtg, n, dh,
                      occ ? dox : nullptr);
@@ -2268,6 +2289,11 @@ static int trace_api(wr_context* c, const wr_ray* rays, const float* targets, in
     else HIPCHK(hipMemcpyAsync(hits, dh, nb * sizeof(wr_hit), hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(hipStreamSynchronize(c->stream));
+  if (c->trace_log && c->fast_on) {
+    DevCounters h;
+    HIPCHK(hipMemcpy(&h, c->ctr, sizeof h, hipMemcpyDeviceToHost));
+    log_rounds(h.rounds);
+  }
   return WR_OK;
 }
 
