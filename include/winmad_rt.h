@@ -571,6 +571,71 @@ int wr_light_radiance_dev(wr_context* ctx, const wr_hit* hits, const float* ray_
 int wr_rng_uniform_dev(wr_context* ctx, uint32_t seed, uint32_t iteration, uint32_t subpath, const uint32_t* path,
                        uint32_t* ctr, int32_t draws, int64_t n, float* out);
 
+/* ---- point sets on the device: radius and k-nearest queries.
+ * Callers detect these entry points by their symbols (WR_API_VERSION stays 8).
+ *
+ * The reference's point KD tree (scene/KDtree.h) as calls on device arrays:
+ * what -vcm, -pr and -mm ask of searchInRadius and -pm of searchKnn
+ * (knnPhotons = 50, maxSqrDis = 0.1).  An index is a hashed grid over a copy of
+ * the caller's points; the answers are exact and a pure function of the arrays,
+ * never of the grid:
+ *   d2(q, p) = sqr_len(q - p) in float: per-component subtraction, then
+ *     x*x + y*y + z*z, each step rounded, no fused multiply-add
+ *     (Vector3::sqrLength).
+ *   Radius queries (KdTree::searchInRadius, KDtree.h:141-173) report point i
+ *     iff sqrtf(d2) < r, strictly, with the correctly rounded square root;
+ *     r = radii[j] when `radii` is given, else `radius`.  count[j] is the
+ *     number of points reported for query j.  wr_points_in_radius_dev writes
+ *     their indices (into the caller's `pos`) at index[offset[j] ..], at most
+ *     offset[j + 1] - offset[j] of them (a list that does not fit is cut
+ *     short), and never outside [0, capacity): a query whose offsets decrease,
+ *     are negative or pass `capacity` writes nothing.  The order inside one
+ *     list is the index's own, not ascending, and deterministic: the same
+ *     arrays give the same bytes, run after run and build after build.
+ *   k-nearest queries (KdTree::searchKnn, KDtree.h:175-208, with
+ *     photonMap.h's ClosePhotonQuery) consider the points with
+ *     d2 < max_sqr_dist (strictly) and return the k smallest in the order of
+ *     (d2, index), ascending: equal d2 goes to the lower index.  count[j] is
+ *     how many were found (<= k); unused slots hold index -1 and sqr_dist 0;
+ *     sqr_dist[j * k + count[j] - 1] is the squared gather radius
+ *     ClosePhotonQuery keeps in kPhotons[0].sqrDis.
+ *   A point with a NaN or infinite coordinate is never reported; a query with
+ *     one reports nothing.
+ * wr_points_build_dev copies what it needs: `pos` may be freed or changed
+ *   afterwards.  The index belongs to the caller (wr_points_free; NULL is a
+ *   no-op); wr_destroy frees the indices of the context that are still alive,
+ *   after which their handles are dead.  n == 0 builds an empty index.  It
+ *   holds 16 bytes per point and 4 per bucket (wr_points_info.device_bytes).
+ * Every array is device memory of the context's device (devices[0] of a
+ *   wr_create_multi context), 4-byte aligned (`offset`: 8-byte).  Stream
+ *   ordering and returning when the outputs are written: as the _dev calls
+ *   above.  nq == 0 succeeds.  Array contents never become a GPU fault.
+ * WR_E_ARG: a null context, n < 0 or nq < 0 (refused before any HIP call); n
+ *   or nq above 2^28; a cell that is not a finite number > 0; k outside 1..64;
+ *   a negative or NaN radius (radii NULL) or max_sqr_dist; capacity < 0; a
+ *   null pointer with a non-zero size (radii excepted); a misaligned pointer;
+ *   a pointer that is not device memory of the context's device; an output
+ *   that overlaps an input or another output; an index of another context. */
+typedef struct wr_points wr_points;   /* an index over a caller's point set, on the context's device */
+typedef struct {
+  int64_t n;              /* points indexed                                   */
+  float   cell;           /* cell edge                                         */
+  float   origin[3];      /* grid origin: the bounding-box minimum of the finite points */
+  int64_t buckets;        /* hash buckets                                      */
+  int64_t max_bucket;     /* most points in one bucket                         */
+  int64_t device_bytes;   /* what the index holds in HBM                       */
+} wr_points_info;
+int wr_points_build_dev(wr_context* ctx, const float* pos /* n*3, device */, int64_t n, float cell, wr_points** out);
+int wr_points_info_get(const wr_points* idx, wr_points_info* out);
+void wr_points_free(wr_points* idx);
+int wr_points_count_dev(wr_context* ctx, const wr_points* idx, const float* q /* nq*3 */, int64_t nq, float radius,
+                        const float* radii /* NULL, or nq radii that replace `radius` */, int32_t* count /* nq */);
+int wr_points_in_radius_dev(wr_context* ctx, const wr_points* idx, const float* q, int64_t nq, float radius,
+                            const float* radii, const int64_t* offset /* nq+1, the caller's exclusive scan of `count` */,
+                            int64_t capacity /* entries `index` holds */, int32_t* index);
+int wr_points_knn_dev(wr_context* ctx, const wr_points* idx, const float* q, int64_t nq, int32_t k, float max_sqr_dist,
+                      int32_t* index /* nq*k */, float* sqr_dist /* nq*k */, int32_t* count /* nq */);
+
 /* ---- output (ImageFilm::outputImage, scene/film.cpp:39-64; BDPT transpose
  * bidirPathTracing.cpp:29-46) ---- scale -> clamp [0,1] -> pow(1/gamma) ->
  * (uchar)(x*255.0); binary PPM (RGB).  transpose != 0 swaps [i][j] <-> [j][i]

@@ -552,6 +552,8 @@ static_assert(sizeof(VcmGroup) <= 4000, "kernel argument block too large");
 #include "wr_pt.h"
 // =============================================================== shading on device arrays
 #include "wr_shade.h"
+// =============================================================== point sets on the device
+#include "wr_points.h"
 
 }  // namespace
 
@@ -817,6 +819,9 @@ struct wr_context {
   // ---- one process per GPU (wr_comm_init): this rank's communicator
   ncclComm_t comm = nullptr;
   int comm_ranks = 0, comm_rank = 0;
+  // ---- point-set indices handed out and still alive (wr_points_build_dev):
+  // wr_destroy frees them
+  std::vector<wr_points*> points;
   wr_context() = default;
   wr_context(const wr_context&) = delete;
   wr_context& operator=(const wr_context&) = delete;
@@ -829,6 +834,18 @@ struct wr_context {
     if (host_ctr) (void)hipHostFree(host_ctr);
     if (stream) (void)hipStreamDestroy(stream);
   }
+};
+
+// An index over a caller's point set (csrc/wr_points.h): bucket-sorted records
+// and the buckets' first records, on the context's device.  Freed with that
+// device current (wr_points_free, wr_destroy).
+struct wr_points {
+  wr_context* ctx = nullptr;
+  int64_t n = 0;  // points given (X.nrec of them finite)
+  PtsIndex X{};
+  int64_t buckets = 0, max_bucket = 0;
+  DevBuf<float4> rec;
+  DevBuf<int> start;
 };
 
 namespace {
@@ -2179,6 +2196,8 @@ void wr_destroy(wr_context* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (Pipe& p : c->pipes)
     if (p.stream) (void)hipStreamSynchronize(p.stream);
+  for (wr_points* x : c->points) delete x;  // indices the caller did not free
+  c->points.clear();
   delete c;
 }
 
@@ -3743,6 +3762,233 @@ int wr_rng_uniform_dev(wr_context* c, uint32_t seed, uint32_t iteration, uint32_
   if (int rc = shade_order(c)) return rc;
   hipLaunchKernelGGL(k_rng_uniform, dim3(g), dim3(256), 0, c->stream, seed, iteration, subpath, path, ctr, draws, n,
                      out);
+  return shade_end(c);
+}
+
+// ---- point sets on the device (wr_points_*; kernels in
+// wr_points.h).  Arguments are checked like those of the shading calls; what
+// the arrays hold (offsets, radii, coordinates) is checked by the kernels.
+struct PtsArg {
+  const void* p;
+  size_t bytes;
+  size_t align;
+  const char* name;
+  bool out;
+  bool optional;
+};
+// the bucket count of n points: 2^k, at least twice the points and one row run
+static uint32_t pts_table(int64_t n) {
+  uint32_t t = kPtsRowW;
+  while (static_cast<int64_t>(t) < 2 * n) t <<= 1;
+  return t;
+}
+// WR_OK and *go = false: nothing to do (nq == 0)
+static int pts_begin(wr_context* c, const wr_points* idx, const char* call, int64_t nq,
+                     std::initializer_list<PtsArg> args, bool* go) {
+  *go = false;
+  const std::string who = std::string(call) + ": ";
+  if (!c) return fail(WR_E_ARG, who + "null context");
+  if (nq < 0) return fail(WR_E_ARG, who + "nq < 0");
+  if (!idx) return fail(WR_E_ARG, who + "null index");
+  if (idx->ctx != c) return fail(WR_E_ARG, who + "the index belongs to another context");
+  if (nq > (int64_t(1) << 28)) return fail(WR_E_ARG, who + "at most 2^28 queries per call");
+  if (nq == 0) return WR_OK;
+  for (const PtsArg& a : args) {
+    if (!a.p && a.bytes && !a.optional) return fail(WR_E_ARG, who + "null " + a.name);
+    if (a.p && reinterpret_cast<uintptr_t>(a.p) % a.align)
+      return fail(WR_E_ARG, who + a.name + " must be " + std::to_string(a.align) + "-byte aligned");
+  }
+  for (const PtsArg& a : args)
+    if (a.p && a.bytes)
+      if (int rc = check_dev_range(c, a.p, a.bytes, (who + a.name).c_str(), "no point-set call: copy it to the device"))
+        return rc;
+  for (const PtsArg& a : args)
+    for (const PtsArg& b : args)
+      if (&a < &b && (a.out || b.out) && a.bytes && b.bytes && ranges_overlap(a.p, a.bytes, b.p, b.bytes))
+        return fail(WR_E_ARG, who + a.name + " overlaps " + b.name);
+  *go = true;
+  return WR_OK;
+}
+
+int wr_points_build_dev(wr_context* c, const float* pos, int64_t n, float cell, wr_points** out) {
+  const std::string who = "wr_points_build_dev: ";
+  if (!c) return fail(WR_E_ARG, who + "null context");
+  if (n < 0) return fail(WR_E_ARG, who + "n < 0");
+  if (!out) return fail(WR_E_ARG, who + "null out");
+  *out = nullptr;
+  if (n > (int64_t(1) << 28)) return fail(WR_E_ARG, who + "at most 2^28 points");
+  if (!(cell > 0.f) || !std::isfinite(cell)) return fail(WR_E_ARG, who + "cell must be a finite number > 0");
+  if (n && !pos) return fail(WR_E_ARG, who + "null pos");
+  if (n && reinterpret_cast<uintptr_t>(pos) % 4) return fail(WR_E_ARG, who + "pos must be 4-byte aligned");
+  if (n)
+    if (int rc = check_dev_range(c, pos, static_cast<size_t>(n) * 12, (who + "pos").c_str(),
+                                 "no point-set call: copy it to the device"))
+      return rc;
+  DeviceGuard dg;
+  if (int rc = shade_order(c)) return rc;
+  const hipStream_t sm = c->stream;
+  const int ni = static_cast<int>(n);
+  const uint32_t T = pts_table(n);
+  std::unique_ptr<wr_points> I(new wr_points);  // (its buffers free on c->device, current until `dg` goes)
+  I->ctx = c;
+  I->n = n;
+  I->buckets = T;
+  if (int rc = I->start.grow(size_t(T) + 1)) return rc;
+  if (n)
+    if (int rc = I->rec.grow(static_cast<size_t>(n))) return rc;
+  PtsIndex& X = I->X;
+  X.rec = I->rec.p;
+  X.start = I->start.p;
+  X.tmask = T - 1;
+  X.cell = cell;
+  DevBuf<uint32_t> small;  // [0..2] the bounding-box minimum (ordered integers), [3] the fullest bucket
+  if (int rc = small.grow(4)) return rc;
+  HIPCHK(hipMemsetAsync(small.p, 0xff, 12, sm));
+  HIPCHK(hipMemsetAsync(small.p + 3, 0, 4, sm));
+  uint32_t h4[4] = {~0u, ~0u, ~0u, 0u};
+  int nrec = 0;
+  if (n) {
+    const int g = static_cast<int>(std::min<int64_t>((n + 255) / 256, 1 << 16));
+    hipLaunchKernelGGL(k_pts_bbox, dim3(g), dim3(256), 0, sm, pos, ni, small.p);
+    HIPCHK(hipMemcpyAsync(h4, small.p, 12, hipMemcpyDeviceToHost, sm));
+    HIPCHK(hipStreamSynchronize(sm));
+    for (int a = 0; a < 3; ++a) {
+      const uint32_t o = h4[a], b = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
+      float f = 0.f;  // no finite point at all: any origin will do
+      if (o != ~0u) std::memcpy(&f, &b, 4);
+      X.org[a] = f;
+    }
+    // (bucket, index) sorted by bucket with a stable radix sort: the order of
+    // the records is a function of the points alone
+    DevBuf<uint32_t> key[2];
+    DevBuf<int> val[2];
+    for (int k = 0; k < 2; ++k) {
+      if (int rc = key[k].grow(static_cast<size_t>(n))) return rc;
+      if (int rc = val[k].grow(static_cast<size_t>(n))) return rc;
+    }
+    int bits = 1;
+    while ((1u << bits) <= T) ++bits;  // keys are 0 .. T
+    size_t tmp_bytes = 0;
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, key[0].p, key[1].p, val[0].p, val[1].p, ni, 0, bits, sm));
+    DevBuf<char> tmp;
+    if (int rc = tmp.grow(std::max<size_t>(tmp_bytes, 1))) return rc;
+    hipLaunchKernelGGL(k_pts_keys, dim3(g), dim3(256), 0, sm, pos, ni, X, key[0].p, val[0].p);
+    HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, key[0].p, key[1].p, val[0].p, val[1].p, ni, 0, bits, sm));
+    hipLaunchKernelGGL(k_pts_records, dim3(g), dim3(256), 0, sm, pos, ni, T, key[1].p, val[1].p, I->rec.p);
+    const int gt = static_cast<int>(std::min<int64_t>((int64_t(T) + 256) / 256, 1 << 16));
+    hipLaunchKernelGGL(k_pts_start, dim3(gt), dim3(256), 0, sm, key[1].p, ni, T, I->start.p);
+    hipLaunchKernelGGL(k_pts_max_bucket, dim3(gt), dim3(256), 0, sm, I->start.p, T, reinterpret_cast<int*>(small.p + 3));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h4 + 3, small.p + 3, 4, hipMemcpyDeviceToHost, sm));
+    HIPCHK(hipMemcpyAsync(&nrec, I->start.p + T, 4, hipMemcpyDeviceToHost, sm));
+    HIPCHK(hipStreamSynchronize(sm));  // the sort's buffers die here, idle
+  } else {
+    X.org[0] = X.org[1] = X.org[2] = 0.f;
+    HIPCHK(hipMemsetAsync(I->start.p, 0, (size_t(T) + 1) * sizeof(int), sm));
+    HIPCHK(hipStreamSynchronize(sm));
+  }
+  X.nrec = nrec;
+  I->max_bucket = h4[3];
+  c->points.push_back(I.get());
+  *out = I.release();
+  return WR_OK;
+}
+
+int wr_points_info_get(const wr_points* idx, wr_points_info* out) {
+  if (!idx || !out) return fail(WR_E_ARG, "wr_points_info_get: null argument");
+  *out = wr_points_info{};
+  out->n = idx->n;
+  out->cell = idx->X.cell;
+  for (int a = 0; a < 3; ++a) out->origin[a] = idx->X.org[a];
+  out->buckets = idx->buckets;
+  out->max_bucket = idx->max_bucket;
+  out->device_bytes = static_cast<int64_t>(idx->rec.n * sizeof(float4) + idx->start.n * sizeof(int));
+  return WR_OK;
+}
+
+void wr_points_free(wr_points* idx) {
+  if (!idx) return;
+  wr_context* c = idx->ctx;
+  DeviceGuard dg;
+  (void)hipSetDevice(c->device);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  c->points.erase(std::remove(c->points.begin(), c->points.end(), idx), c->points.end());
+  delete idx;
+}
+
+static int pts_radius_call(wr_context* c, const wr_points* idx, const char* call, bool fill, const float* q,
+                           int64_t nq, float radius, const float* radii, const int64_t* offset, int64_t capacity,
+                           int32_t* count, int32_t* index) {
+  const std::string who = std::string(call) + ": ";
+  if (c && nq >= 0) {
+    if (!radii && !(radius >= 0.f)) return fail(WR_E_ARG, who + "radius must not be negative or NaN");
+    if (fill && capacity < 0) return fail(WR_E_ARG, who + "capacity < 0");
+    if (fill && capacity > (int64_t(1) << 40)) return fail(WR_E_ARG, who + "capacity above 2^40");
+  }
+  const size_t nb = nq > 0 ? static_cast<size_t>(nq) : 0, cb = capacity > 0 ? static_cast<size_t>(capacity) : 0;
+  bool go;
+  int rc;
+  if (fill)
+    rc = pts_begin(c, idx, call, nq,
+                   {{q, nb * 12, 4, "q", false, false}, {radii, nb * 4, 4, "radii", false, true},
+                    {offset, (nb + 1) * 8, 8, "offset", false, false}, {index, cb * 4, 4, "index", true, false}}, &go);
+  else
+    rc = pts_begin(c, idx, call, nq,
+                   {{q, nb * 12, 4, "q", false, false}, {radii, nb * 4, 4, "radii", false, true},
+                    {count, nb * 4, 4, "count", true, false}}, &go);
+  if (rc || !go) return rc;
+  DeviceGuard dg;
+  if (int r2 = shade_order(c)) return r2;
+#if WR_PTS_RADIUS_WAVE  // a wave per query (the faster of the two forms, profiles/r18/points)
+  const int g = static_cast<int>((nq + 3) / 4);
+  if (fill)
+    hipLaunchKernelGGL(k_pts_radius_wave<true>, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, radius, radii, offset,
+                       capacity, static_cast<int32_t*>(nullptr), index);
+  else
+    hipLaunchKernelGGL(k_pts_radius_wave<false>, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, radius, radii,
+                       static_cast<const int64_t*>(nullptr), int64_t(0), count, static_cast<int32_t*>(nullptr));
+#else  // a lane per query
+  const int g = static_cast<int>((nq + 255) / 256);
+  if (fill)
+    hipLaunchKernelGGL(k_pts_radius<true>, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, radius, radii, offset,
+                       capacity, static_cast<int32_t*>(nullptr), index);
+  else
+    hipLaunchKernelGGL(k_pts_radius<false>, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, radius, radii,
+                       static_cast<const int64_t*>(nullptr), int64_t(0), count, static_cast<int32_t*>(nullptr));
+#endif
+  return shade_end(c);
+}
+
+int wr_points_count_dev(wr_context* c, const wr_points* idx, const float* q, int64_t nq, float radius,
+                        const float* radii, int32_t* count) {
+  return pts_radius_call(c, idx, "wr_points_count_dev", false, q, nq, radius, radii, nullptr, 0, count, nullptr);
+}
+
+int wr_points_in_radius_dev(wr_context* c, const wr_points* idx, const float* q, int64_t nq, float radius,
+                            const float* radii, const int64_t* offset, int64_t capacity, int32_t* index) {
+  return pts_radius_call(c, idx, "wr_points_in_radius_dev", true, q, nq, radius, radii, offset, capacity, nullptr,
+                         index);
+}
+
+int wr_points_knn_dev(wr_context* c, const wr_points* idx, const float* q, int64_t nq, int32_t k, float max_sqr_dist,
+                      int32_t* index, float* sqr_dist, int32_t* count) {
+  const std::string who = "wr_points_knn_dev: ";
+  if (c && nq >= 0) {
+    if (k < 1 || k > 64) return fail(WR_E_ARG, who + "k must be 1..64");
+    if (!(max_sqr_dist >= 0.f)) return fail(WR_E_ARG, who + "max_sqr_dist must not be negative or NaN");
+  }
+  const size_t nb = nq > 0 ? static_cast<size_t>(nq) : 0, kb = nb * static_cast<size_t>(k > 0 ? k : 0) * 4;
+  bool go;
+  if (int rc = pts_begin(c, idx, "wr_points_knn_dev", nq,
+                         {{q, nb * 12, 4, "q", false, false}, {index, kb, 4, "index", true, false},
+                          {sqr_dist, kb, 4, "sqr_dist", true, false}, {count, nb * 4, 4, "count", true, false}}, &go))
+    return rc;
+  if (!go) return WR_OK;
+  DeviceGuard dg;
+  if (int rc = shade_order(c)) return rc;
+  const int g = static_cast<int>((nq + 3) / 4);  // a wave per query
+  hipLaunchKernelGGL(k_pts_knn, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, k, max_sqr_dist, index, sqr_dist,
+                     count);
   return shade_end(c);
 }
 

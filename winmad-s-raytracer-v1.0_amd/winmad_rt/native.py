@@ -29,7 +29,9 @@ EXPORTS = ["wr_scene_load", "wr_scene_from_desc", "wr_scene_info_get", "wr_scene
            "wr_render_path_moments", "wr_film_error", "wr_render_features", "wr_film_denoise",
            "wr_camera_rays", "wr_trace_closest_dev", "wr_occluded_dev", "wr_path_radiance_dev",
            "wr_bsdf_eval_dev", "wr_bsdf_sample_dev", "wr_light_illuminate_dev", "wr_light_emit_dev",
-           "wr_light_radiance_dev", "wr_rng_uniform_dev"]
+           "wr_light_radiance_dev", "wr_rng_uniform_dev",
+           "wr_points_build_dev", "wr_points_info_get", "wr_points_free", "wr_points_count_dev",
+           "wr_points_in_radius_dev", "wr_points_knn_dev"]
 CKPT_BDPT, CKPT_VCM, CKPT_PT = 1, 2, 3
 FILM_PT, FILM_BDPT = 0, 1
 
@@ -118,6 +120,11 @@ class WrDenoiseParams(C.Structure):
 
     def __init__(self, levels=5, normal_power=7, sigma_l=4.0, sigma_p=0.05, sigma_a=0.1):
         super().__init__(levels, normal_power, sigma_l, sigma_p, sigma_a)
+
+
+class WrPointsInfo(C.Structure):
+    _fields_ = [("n", C.c_int64), ("cell", C.c_float), ("origin", C.c_float * 3), ("buckets", C.c_int64),
+                ("max_bucket", C.c_int64), ("device_bytes", C.c_int64)]
 
 
 class WrError(RuntimeError):
@@ -227,6 +234,13 @@ def lib():
         L.wr_light_emit_dev.argtypes = [P, P, P, P, I64, P]
         L.wr_light_radiance_dev.argtypes = [P, P, P, I64, P]
         L.wr_rng_uniform_dev.argtypes = [P, U32, U32, U32, P, P, C.c_int32, I64, P]
+        L.wr_points_build_dev.argtypes = [P, P, I64, C.c_float, C.POINTER(P)]
+        L.wr_points_info_get.argtypes = [P, C.POINTER(WrPointsInfo)]
+        L.wr_points_free.argtypes = [P]
+        L.wr_points_free.restype = None
+        L.wr_points_count_dev.argtypes = [P, P, P, I64, C.c_float, P, P]
+        L.wr_points_in_radius_dev.argtypes = [P, P, P, I64, C.c_float, P, P, I64, P]
+        L.wr_points_knn_dev.argtypes = [P, P, P, I64, C.c_int32, C.c_float, P, P, P]
         L.wr_last_error.restype = C.c_char_p
         _lib = L
     return _lib
@@ -504,6 +518,8 @@ class Context:
         check(lib().wr_set_trace_mode(self.h, mode))
 
     def close(self):
+        for idx in list(getattr(self, "_points", ())):  # the indices handed out go first (wr_destroy would free them)
+            idx.close()
         if getattr(self, "h", None):
             lib().wr_destroy(self.h)
             self.h = None
@@ -713,6 +729,14 @@ class Context:
         check(lib().wr_rng_uniform_dev(self.h, seed, iteration, subpath, ptr(path), ptr(ctr), draws, n, ptr(out)))
         return out
 
+    # ---- point sets on the device (wr_points_*)
+    def points_index_t(self, pos, cell):
+        """wr_points_build_dev: an index over pos, a torch float32 (n, 3) tensor on
+        the context's device (copied: pos may change afterwards).  Returns a
+        PointsIndex; close it (or leave a `with` block) before the context --
+        the context's close closes the indices it handed out."""
+        return PointsIndex(self, pos, cell)
+
     def render_bdpt(self, width, height, iterations=1, seed=5489, iter_begin=0, control_length=3,
                     max_path_length=10, faithful=1, time_kernels=0, count_work=0, film=None, film_ptr=None):
         """BidirPathTracing::render.  Host film (numpy, accumulated) or a device
@@ -845,6 +869,132 @@ class Context:
         opt = [C.c_void_p(x) if x is not None else None for x in (normal_ptr, position_ptr, albedo_ptr)]
         check(lib().wr_film_denoise(self.h, C.c_void_p(film_ptr), C.c_void_p(film_sq_ptr), width, height, n_passes,
                                     *opt, C.byref(p), 1, C.c_void_p(out_ptr)))
+
+
+class PointsIndex:
+    """An index over a point set on the device (include/winmad_rt.h wr_points_*):
+    exact radius and k-nearest queries, KdTree::searchInRadius / searchKnn.
+    Tensors and streams as the Context's _t calls; a context manager."""
+
+    def __init__(self, ctx, pos, cell):
+        self.h = None
+        self.ctx = ctx
+        cell = float(cell)
+        if not (cell > 0.0 and cell < float("inf")):
+            raise ValueError(f"cell must be a finite number > 0, got {cell!r}")
+        _dev_tensor(pos, "pos", (None, 3), "float32", None)
+        ctx._dev_args((pos, "pos", (None, 3), "float32"))
+        h = C.c_void_p()
+        check(lib().wr_points_build_dev(ctx.h, C.c_void_p(pos.data_ptr()), pos.shape[0], cell, C.byref(h)))
+        self.h = h
+        if not hasattr(ctx, "_points"):
+            ctx._points = []
+        ctx._points.append(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().wr_points_free(self.h)
+            self.h = None
+            self.ctx._points.remove(self)
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        out = WrPointsInfo()
+        check(lib().wr_points_info_get(self.h, C.byref(out)))
+        return {"n": out.n, "cell": out.cell, "origin": tuple(out.origin), "buckets": out.buckets,
+                "max_bucket": out.max_bucket, "device_bytes": out.device_bytes}
+
+    @staticmethod
+    def _radius_args(q, radius, radii):
+        """(nq, radius as float): exactly one of radius / radii is given, and q is checked."""
+        if (radius is None) == (radii is None):
+            raise ValueError("give exactly one of radius (a number) and radii (an (nq,) float32 tensor)")
+        if radius is not None:
+            radius = float(radius)
+            if not radius >= 0.0:
+                raise ValueError(f"radius must not be negative or NaN, got {radius!r}")
+        _dev_tensor(q, "q", (None, 3), "float32", None)
+        nq = q.shape[0]
+        if radii is not None:
+            _dev_tensor(radii, "radii", (nq,), "float32", None)
+            return nq, 0.0
+        return nq, radius
+
+    def count_t(self, q, radius=None, radii=None, out=None):
+        """wr_points_count_dev: for each row of q ((nq, 3) float32) the number of
+        points with |q - p| < radius (or radii[j]), as an int32 (nq,) tensor
+        (`out` when given)."""
+        import torch
+        nq, r = self._radius_args(q, radius, radii)
+        if out is None:
+            out = torch.empty((nq,), dtype=torch.int32, device=q.device)
+        specs = [(q, "q", (nq, 3), "float32"), (out, "out", (nq,), "int32")]
+        if radii is not None:
+            specs.append((radii, "radii", (nq,), "float32"))
+        self.ctx._dev_args(*specs)
+        check(lib().wr_points_count_dev(self.ctx.h, self.h, C.c_void_p(q.data_ptr()), nq, r,
+                                        C.c_void_p(radii.data_ptr()) if radii is not None else None,
+                                        C.c_void_p(out.data_ptr())))
+        return out
+
+    def fill_t(self, q, offset, index, radius=None, radii=None):
+        """wr_points_in_radius_dev with the caller's offsets ((nq + 1,) int64) and
+        index buffer ((capacity,) int32), written in place: query j's indices
+        at index[offset[j]:], at most offset[j + 1] - offset[j] of them."""
+        nq, r = self._radius_args(q, radius, radii)
+        specs = [(q, "q", (nq, 3), "float32"), (offset, "offset", (nq + 1,), "int64"),
+                 (index, "index", (None,), "int32")]
+        if radii is not None:
+            specs.append((radii, "radii", (nq,), "float32"))
+        for spec in specs:
+            _dev_tensor(*spec, None)
+        self.ctx._dev_args(*specs)
+        check(lib().wr_points_in_radius_dev(self.ctx.h, self.h, C.c_void_p(q.data_ptr()), nq, r,
+                                            C.c_void_p(radii.data_ptr()) if radii is not None else None,
+                                            C.c_void_p(offset.data_ptr()), index.shape[0],
+                                            C.c_void_p(index.data_ptr())))
+        return index
+
+    def in_radius_t(self, q, radius=None, radii=None):
+        """The points within the radius of each query: (offset, index), an int64
+        (nq + 1,) exclusive scan of the counts and the int32 indices into
+        `pos`, query j's at index[offset[j]:offset[j + 1]] in the index's own
+        (deterministic, not ascending) order.  Count, torch.cumsum, fill: the
+        scan never leaves the device."""
+        import torch
+        cnt = self.count_t(q, radius, radii)
+        offset = torch.zeros((cnt.shape[0] + 1,), dtype=torch.int64, device=q.device)
+        offset[1:] = torch.cumsum(cnt, 0, dtype=torch.int64)
+        index = torch.empty((int(offset[-1]),), dtype=torch.int32, device=q.device)
+        return offset, self.fill_t(q, offset, index, radius, radii)
+
+    def knn_t(self, q, k, max_sqr_dist):
+        """wr_points_knn_dev: of the points with d2 < max_sqr_dist the k nearest
+        of each query, by (d2, index): (index (nq, k) int32, sqr_dist (nq, k)
+        float32, count (nq,) int32); unused slots hold -1 and 0."""
+        import torch
+        if not isinstance(k, int) or not 1 <= k <= 64:
+            raise ValueError(f"k must be an int in 1..64, got {k!r}")
+        max_sqr_dist = float(max_sqr_dist)
+        if not max_sqr_dist >= 0.0:
+            raise ValueError(f"max_sqr_dist must not be negative or NaN, got {max_sqr_dist!r}")
+        _dev_tensor(q, "q", (None, 3), "float32", None)
+        nq = q.shape[0]
+        index = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+        sqr = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        cnt = torch.empty((nq,), dtype=torch.int32, device=q.device)
+        self.ctx._dev_args((q, "q", (nq, 3), "float32"))
+        check(lib().wr_points_knn_dev(self.ctx.h, self.h, C.c_void_p(q.data_ptr()), nq, k, max_sqr_dist,
+                                      C.c_void_p(index.data_ptr()), C.c_void_p(sqr.data_ptr()),
+                                      C.c_void_p(cnt.data_ptr())))
+        return index, sqr, cnt
 
 
 def film_denoise(film, film_sq, n_passes, normal=None, position=None, albedo=None, **params):
