@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "winmad_rt.h"
+#include "wr_args.h"
 #include "wr_flatten.h"
 #include "wr_scene.h"
 #include "wr_traverse.h"
@@ -2206,28 +2207,51 @@ void wr_destroy(wr_context* c) {
 static int api_scratch(wr_context* c, size_t bytes) { return c->api_tmp.grow(bytes); }
 
 // ---- device-resident ray batches (wr_*_dev, wr_camera_rays).
-// A caller's mistake must not become a GPU fault: every pointer of a _dev call
-// is looked up (its first and last byte) and has to be device memory of the
-// context's device.  A failed query leaves HIP's sticky error set: cleared here.
-static int check_dev_range(const wr_context* c, const void* p, size_t bytes, const char* what,
-                           const char* host_call) {
-  const char* b = static_cast<const char*>(p);
-  for (const char* q : {b, b + (bytes ? bytes - 1 : 0)}) {
-    hipPointerAttribute_t at{};
-    const hipError_t e = hipPointerGetAttributes(&at, q);
-    if (e != hipSuccess) (void)hipGetLastError();
-    if (e != hipSuccess || at.type != hipMemoryTypeDevice)
-      return fail(WR_E_ARG, std::string(what) + " is not device memory (host or pinned host memory goes to " +
-                                host_call + ")");
-    if (at.device != c->device)
-      return fail(WR_E_ARG, std::string(what) + " lives on device " + std::to_string(at.device) +
-                                ", the context on device " + std::to_string(c->device));
-  }
+// The arrays of every call that takes device arrays go through wr_args.h's
+// checker, with HIP's pointer lookup as its classifier.  A failed query leaves
+// HIP's sticky error set: cleared here.
+static wr::PtrClass classify_pointer(const void* p) {
+  hipPointerAttribute_t at{};
+  const hipError_t e = hipPointerGetAttributes(&at, p);
+  if (e != hipSuccess) (void)hipGetLastError();
+  return {e == hipSuccess, at.type == hipMemoryTypeDevice, at.device};
+}
+static int check_dev_args(const wr_context* c, const char* call, std::initializer_list<wr::Arg> args,
+                          const char* host_goes_to) {
+  const wr::ArgError e = wr::check_args(call, args, c->device, host_goes_to, classify_pointer);
+  return e ? fail(e.code, e.msg) : WR_OK;
+}
+// the context's device current, its stream after the caller's work on the
+// legacy null stream (like a render): before the first operation an array call
+// enqueues
+static int api_order(wr_context* c) {
+  HIPCHK(hipSetDevice(c->device));
+  (void)hipEventRecord(c->t_null, nullptr);
+  (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
   return WR_OK;
 }
-static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return a && b && x < y + nb && y < x + na;
+static int api_finish(wr_context* c) {
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return WR_OK;
+}
+
+// One queue of nb rays traced on the context stream with the context's own
+// counters, t2 scratch and spill area (the API calls' trace; the renders' is
+// tslot).  count: the counting kernels (WR_TRACE_LOG).
+static int api_trace(wr_context* c, const RayQueue& rays, size_t nb, bool count, int mode) {
+  c->timing = false;
+  Timer tm(c, nullptr);
+  HIPCHK(hipMemsetAsync(c->ctr, 0, sizeof(DevCounters), c->stream));
+  if (c->fast_on)
+    if (int rc = c->api_t2.grow(5 * nb)) return rc;  // as ensure_t2
+  QueueList ql;
+  ql.add(rays, static_cast<int>(nb));
+  if (c->fast_on && !c->api_spill.p && max_spill_entries(c) > 0)
+    if (int rc = c->api_spill.grow(max_spill_entries(c) * size_t(c->fast_blocks) * 64)) return rc;
+  const TraceSlot ts{&c->ctr->fetch, c->api_t2.p, c->api_t2.n / 5, &c->ctr->hard[0], c->api_spill.p, &c->ctr->rlist};
+  trace_launch(c, c->stream, c->ctr, ts, tm, count, ql.Q, ql.max_rays, c->api_dense ? TRACE_DENSE : mode, true);
+  return WR_OK;
 }
 
 // wr_trace_closest / wr_occluded and their _dev forms: prep kernel -> SoA queue
@@ -2243,20 +2267,17 @@ static int trace_api(wr_context* c, const wr_ray* rays, const float* targets, in
   const int n = static_cast<int>(n64);
   const size_t nb = size_t(n);
   if (on_device) {
-    const char* host_call = occ ? "wr_occluded" : "wr_trace_closest";
-    if (int rc = check_dev_range(c, rays, nb * sizeof(wr_ray), "rays", host_call)) return rc;
-    if (occ) {
-      if (int rc = check_dev_range(c, targets, nb * 12, "targets", host_call)) return rc;
-      if (int rc = check_dev_range(c, occ, nb, "occluded", host_call)) return rc;
-      if (ranges_overlap(occ, nb, rays, nb * sizeof(wr_ray)) || ranges_overlap(occ, nb, targets, nb * 12))
-        return fail(WR_E_ARG, "occluded overlaps an input");
-    } else {
-      if (int rc = check_dev_range(c, hits, nb * sizeof(wr_hit), "hits", host_call)) return rc;
-      if (ranges_overlap(hits, nb * sizeof(wr_hit), rays, nb * sizeof(wr_ray)))
-        return fail(WR_E_ARG, "hits overlaps rays");
-    }
+    const wr::Arg in = wr::in(rays, nb * sizeof(wr_ray), "rays");
+    if (int rc = occ ? check_dev_args(c, "wr_occluded_dev",
+                                      {in, wr::in(targets, nb * 12, "targets"), wr::out(occ, nb, "occluded")},
+                                      "wr_occluded")
+                     : check_dev_args(c, "wr_trace_closest_dev", {in, wr::out(hits, nb * sizeof(wr_hit), "hits")},
+                                      "wr_trace_closest"))
+      return rc;
+    if (int rc = api_order(c)) return rc;
+  } else {  // (stages its own copies on the stream: nothing of the caller's to wait for)
+    HIPCHK(hipSetDevice(c->device));
   }
-  HIPCHK(hipSetDevice(c->device));
   // one scratch block: rays, SoA queue, results, counters (kept on the
   // context: no allocation per call, nothing to free on an error return)
   const size_t bytes = nb * ((on_device ? 0 : sizeof(wr_ray) + 12 + sizeof(wr_hit) + 1) + 4 * 11) + 16 * 256;
@@ -2275,11 +2296,7 @@ static int trace_api(wr_context* c, const wr_ray* rays, const float* targets, in
   wr_hit* dh = on_device ? hits : reinterpret_cast<wr_hit*>(take(nb * sizeof(wr_hit)));
   uint8_t* dox = on_device ? occ : reinterpret_cast<uint8_t*>(take(nb));
   int* cnt = reinterpret_cast<int*>(take(sizeof(int)));
-  if (on_device) {
-    // after the caller's work on the legacy null stream, like a render
-    (void)hipEventRecord(c->t_null, nullptr);
-    (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
-  } else {
+  if (!on_device) {
     HIPCHK(hipMemcpyAsync(const_cast<wr_ray*>(dr), rays, nb * sizeof(wr_ray), hipMemcpyHostToDevice, c->stream));
     if (occ)
       HIPCHK(hipMemcpyAsync(const_cast<float*>(dtg), targets, nb * 12, hipMemcpyHostToDevice, c->stream));
@@ -2287,19 +2304,10 @@ static int trace_api(wr_context* c, const wr_ray* rays, const float* targets, in
   HIPCHK(hipMemcpyAsync(cnt, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
   const int g = std::max(1, std::min(c->grid, (n + 255) / 256));
   hipLaunchKernelGGL(k_api_prep, dim3(g), dim3(256), 0, c->stream, dr, n, occ ? 1 : 0, o3, d3, tmn, tmx, dtg, dcut);
-  c->timing = false;
-  Timer tm(c, nullptr);
-  HIPCHK(hipMemsetAsync(c->ctr, 0, sizeof(DevCounters), c->stream));
-  if (c->fast_on)
-    if (int rc = c->api_t2.grow(5 * nb)) return rc;  // as ensure_t2
-  QueueList ql;
-  ql.add(rq(o3, d3, n, cnt, tt, pr, occ ? dcut : nullptr, tmn, tmx), n);
-  if (c->fast_on && !c->api_spill.p && max_spill_entries(c) > 0)
-    if (int rc = c->api_spill.grow(max_spill_entries(c) * size_t(c->fast_blocks) * 64)) return rc;
-  const TraceSlot ts{&c->ctr->fetch, c->api_t2.p, c->api_t2.n / 5, &c->ctr->hard[0], c->api_spill.p, &c->ctr->rlist};
   // (WR_TRACE_LOG: the counting kernels, for the rounds line below)
-  trace_launch(c, c->stream, c->ctr, ts, tm, c->trace_log, ql.Q, ql.max_rays,
-               c->api_dense ? TRACE_DENSE : (occ != nullptr ? TRACE_CUT : TRACE_PLAIN), true);
+  if (int rc = api_trace(c, rq(o3, d3, n, cnt, tt, pr, occ ? dcut : nullptr, tmn, tmx), nb, c->trace_log,
+                         occ ? TRACE_CUT : TRACE_PLAIN))
+    return rc;
   hipLaunchKernelGGL(k_api_finish, dim3(g), dim3(256), 0, c->stream, c->ds, o3, d3, tt, pr, dtg, n, dh,
                      occ ? dox : nullptr);
   HIPCHK(hipGetLastError());
@@ -3004,13 +3012,12 @@ static int path_radiance_one(wr_context* c, const wr_ray* rays, int64_t n64, int
   const int P = static_cast<int>(n64);
   const size_t nf = size_t(P) * 3;
   if (on_device) {
-    const size_t rb = size_t(P) * sizeof(wr_ray), fb = nf * sizeof(float);
-    if (int rc = check_dev_range(c, rays, rb, "rays", "wr_path_radiance")) return rc;
-    if (int rc = check_dev_range(c, rgb, fb, "rgb", "wr_path_radiance")) return rc;
-    if (rgb_sq)
-      if (int rc = check_dev_range(c, rgb_sq, fb, "rgb_sq", "wr_path_radiance")) return rc;
-    if (ranges_overlap(rgb, fb, rays, rb) || ranges_overlap(rgb_sq, fb, rays, rb) || ranges_overlap(rgb, fb, rgb_sq, fb))
-      return fail(WR_E_ARG, "rgb / rgb_sq overlap an input or each other");
+    const size_t fb = nf * sizeof(float);
+    if (int rc = check_dev_args(c, "wr_path_radiance_dev",
+                                {wr::in(rays, size_t(P) * sizeof(wr_ray), "rays"),
+                                 wr::out(rgb, fb, "rgb"), wr::out(rgb_sq, fb, "rgb_sq", 1, true)},
+                                "wr_path_radiance"))
+      return rc;
   }
   HIPCHK(hipSetDevice(c->device));
   const double t0 = host_now();
@@ -3439,11 +3446,8 @@ int wr_film_error(wr_context* c, const float* film, const float* film_sq, int wi
     }
   } else {
     DeviceGuard dg;
-    HIPCHK(hipSetDevice(c->device));
+    if (int rc = api_order(c)) return rc;
     if (int rc = c->err_acc.grow(4)) return rc;
-    // after the caller's work on the legacy null stream, like a render
-    (void)hipEventRecord(c->t_null, nullptr);
-    (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
     HIPCHK(hipMemsetAsync(c->err_acc.p, 0, sizeof acc, c->stream));
     const size_t blocks = (nf + kErrBlock - 1) / kErrBlock;
     const int g = static_cast<int>(std::max<size_t>(1, std::min<size_t>(blocks, size_t(c->cus) * 8)));
@@ -3472,7 +3476,7 @@ int wr_render_features(wr_context* c, int32_t width, int32_t height, int layout,
   if (layout != WR_FILM_PT && layout != WR_FILM_BDPT) return fail(WR_E_ARG, "layout must be WR_FILM_PT or WR_FILM_BDPT");
   if (!normal && !albedo && !position && !depth) return fail(WR_E_ARG, "no output film");
   DeviceGuard dg;
-  HIPCHK(hipSetDevice(c->device));
+  if (int rc = api_order(c)) return rc;
   const double t0 = host_now();
   const int n = width * height;
   const size_t nb = size_t(n);
@@ -3493,23 +3497,10 @@ int wr_render_features(wr_context* c, int32_t width, int32_t height, int layout,
     if (position) dp = reinterpret_cast<float*>(take(nb * 12));
     if (depth) dd = reinterpret_cast<float*>(take(nb * 4));
   }
-  // after the caller's work on the legacy null stream, like a render
-  (void)hipEventRecord(c->t_null, nullptr);
-  (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
   HIPCHK(hipMemcpyAsync(cnt, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
   const int g = std::max(1, std::min(c->grid, (n + 255) / 256));
   hipLaunchKernelGGL(k_feat_gen, dim3(g), dim3(256), 0, c->stream, c->ds, width, height, layout, o3, d3);
-  c->timing = false;
-  Timer tm(c, nullptr);
-  HIPCHK(hipMemsetAsync(c->ctr, 0, sizeof(DevCounters), c->stream));
-  if (c->fast_on)
-    if (int rc = c->api_t2.grow(5 * nb)) return rc;  // as ensure_t2
-  QueueList ql;
-  ql.add(rq(o3, d3, n, cnt, tt, pr), n);
-  if (c->fast_on && !c->api_spill.p && max_spill_entries(c) > 0)
-    if (int rc = c->api_spill.grow(max_spill_entries(c) * size_t(c->fast_blocks) * 64)) return rc;
-  const TraceSlot ts{&c->ctr->fetch, c->api_t2.p, c->api_t2.n / 5, &c->ctr->hard[0], c->api_spill.p, &c->ctr->rlist};
-  trace_launch(c, c->stream, c->ctr, ts, tm, false, ql.Q, ql.max_rays, c->api_dense ? TRACE_DENSE : TRACE_PLAIN, true);
+  if (int rc = api_trace(c, rq(o3, d3, n, cnt, tt, pr), nb, false, TRACE_PLAIN)) return rc;
   hipLaunchKernelGGL(k_feat_finish, dim3(g), dim3(256), 0, c->stream, c->ds, c->nmats, o3, d3, tt, pr, width, height,
                      dn_, da, dp, dd);
   HIPCHK(hipGetLastError());
@@ -3546,7 +3537,7 @@ int wr_film_denoise(wr_context* c, const float* film, const float* film_sq, int 
     return WR_OK;
   }
   DeviceGuard dg;
-  HIPCHK(hipSetDevice(c->device));
+  if (int rc = api_order(c)) return rc;
   const int W = width, H = height, npix = W * H;
   const bool guides = normal || position || albedo;
   if (int rc = c->dn_cv[0].grow(size_t(npix))) return rc;
@@ -3559,9 +3550,6 @@ int wr_film_denoise(wr_context* c, const float* film, const float* film_sq, int 
   dn::F4* g2 = guides ? g1 + npix : nullptr;
   const dn::Cfg k{p.sigma_l, p.sigma_p, p.sigma_a, p.normal_power, normal != nullptr, position != nullptr,
                   albedo != nullptr};
-  // after the caller's work on the legacy null stream, like a render
-  (void)hipEventRecord(c->t_null, nullptr);
-  (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
   const int gp = std::max(1, std::min(c->cus * 8, (npix + 255) / 256));
   hipLaunchKernelGGL(dn::k_dn_prepare, dim3(gp), dim3(256), 0, c->stream, film, film_sq, normal, position, albedo,
                      npix, n_passes, c->dn_cv[0].p, g0, g1, g2);
@@ -3578,9 +3566,7 @@ int wr_film_denoise(wr_context* c, const float* film, const float* film_sq, int 
                     : (last ? dn::k_dn_level<false, true> : dn::k_dn_level<false, false>);
     hipLaunchKernelGGL(kern, dim3(gl), dim3(dn::kBlock), shm, c->stream, src, k, W, H, s, dst, out, scale);
   }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return WR_OK;
+  return api_finish(c);
 }
 
 int wr_path_radiance(wr_context* c, const wr_ray* rays, int64_t n64, int32_t max_depth, uint32_t seed,
@@ -3608,17 +3594,16 @@ int wr_camera_rays(wr_context* c, int32_t width, int32_t height, int layout, wr_
   const int n = width * height;
   const size_t bytes = size_t(n) * sizeof(wr_ray);
   if (rays_on_device)
-    if (int rc = check_dev_range(c, rays, bytes, "rays", "wr_camera_rays with rays_on_device = 0")) return rc;
+    if (int rc = check_dev_args(c, "wr_camera_rays", {wr::out(rays, bytes, "rays")},
+                                "wr_camera_rays with rays_on_device = 0"))
+      return rc;
   DeviceGuard dg;
-  HIPCHK(hipSetDevice(c->device));
+  if (int rc = api_order(c)) return rc;
   wr_ray* dr = rays;
   if (!rays_on_device) {
     if (int rc = api_scratch(c, bytes)) return rc;
     dr = reinterpret_cast<wr_ray*>(c->api_tmp.p);
   }
-  // after the caller's work on the legacy null stream, like a render
-  (void)hipEventRecord(c->t_null, nullptr);
-  (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
   const int g = std::max(1, std::min(c->grid, (n + 255) / 256));
   hipLaunchKernelGGL(k_camera_rays, dim3(g), dim3(256), 0, c->stream, c->ds, width, height, layout, dr);
   HIPCHK(hipGetLastError());
@@ -3631,161 +3616,101 @@ int wr_camera_rays(wr_context* c, int32_t width, int32_t height, int layout, wr_
 // DESIGN.md 13; kernels in wr_shade.h).  The arguments are checked as those of
 // the _dev calls above, on the host and before any HIP call where that is
 // possible; the indices inside the arrays are checked by the kernels.
-struct ShadeArg {
-  const void* p;
-  size_t rec;  // bytes per record
-  const char* name;
-  bool out;       // written (in/out counts): must not overlap any other array
-  bool optional;  // may be null
-};
-// WR_OK and *grid = 0: nothing to do (n == 0), else the launch grid.
-static int shade_begin(wr_context* c, const char* call, int64_t n, bool lights, std::initializer_list<ShadeArg> args,
-                       int* grid) {
-  *grid = 0;
+// n records of `rec` bytes (0 for an n the call refuses)
+static size_t recs(int64_t n, size_t rec) { return n > 0 ? static_cast<size_t>(n) * rec : 0; }
+// The frame of a shading call: the scalars and the arrays checked, then
+// launch(grid) on the context stream between api_order and api_finish.
+static int shade_call(wr_context* c, const char* call, int64_t n, bool lights, std::initializer_list<wr::Arg> args,
+                      const std::function<void(int)>& launch) {
   const std::string who = std::string(call) + ": ";
   if (!c) return fail(WR_E_ARG, who + "null context");
   if (n < 0) return fail(WR_E_ARG, who + "n < 0");
   if (n == 0) return WR_OK;
   if (n > (int64_t(1) << 28)) return fail(WR_E_ARG, who + "at most 2^28 records per call");
-  for (const ShadeArg& a : args)
-    if (!a.p && !a.optional) return fail(WR_E_ARG, who + "null " + a.name);
-  if (lights && c->ds.nlights <= 0) return fail(WR_E_SCENE, who + "the scene has no area light");
-  const size_t nb = static_cast<size_t>(n);
-  for (const ShadeArg& a : args)
-    if (a.p)
-      if (int rc = check_dev_range(c, a.p, nb * a.rec, (who + a.name).c_str(), "no shading call: copy it to the device"))
-        return rc;
-  for (const ShadeArg& a : args)
-    for (const ShadeArg& b : args)
-      if (&a < &b && (a.out || b.out) && ranges_overlap(a.p, nb * a.rec, b.p, nb * b.rec))
-        return fail(WR_E_ARG, who + a.name + " overlaps " + b.name);
+  if (lights) {  // refused after a null array, before any pointer is looked up
+    if (const wr::ArgError e = wr::check_args_host(call, args)) return fail(e.code, e.msg);
+    if (c->ds.nlights <= 0) return fail(WR_E_SCENE, who + "the scene has no area light");
+  }
+  if (int rc = check_dev_args(c, call, args, "no shading call: copy it to the device")) return rc;
+  DeviceGuard dg;
+  if (int rc = api_order(c)) return rc;
   // a block per 256 records (at most 2^20 blocks): the records cost unequal time, and blocks
   // that come and go balance the CUs better than c->grid resident ones looping
-  *grid = static_cast<int>((n + 255) / 256);
-  return WR_OK;
-}
-// the context's device current, its stream after the caller's work on the legacy null stream (like a render)
-static int shade_order(wr_context* c) {
-  HIPCHK(hipSetDevice(c->device));
-  (void)hipEventRecord(c->t_null, nullptr);
-  (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
-  return WR_OK;
-}
-static int shade_end(wr_context* c) {
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return WR_OK;
+  launch(static_cast<int>((n + 255) / 256));
+  return api_finish(c);
 }
 
 int wr_bsdf_eval_dev(wr_context* c, const wr_hit* hits, const float* wi, const float* wo, int64_t n,
                      wr_bsdf_info* info, wr_bsdf_eval* out) {
-  int g;
-  if (int rc = shade_begin(c, "wr_bsdf_eval_dev", n, false,
-                           {{hits, sizeof(wr_hit), "hits", false, false}, {wi, 12, "wi", false, false},
-                            {wo, 12, "wo", false, false}, {info, sizeof(wr_bsdf_info), "info", true, true},
-                            {out, sizeof(wr_bsdf_eval), "out", true, false}}, &g))
-    return rc;
-  if (!g) return WR_OK;
-  DeviceGuard dg;
-  if (int rc = shade_order(c)) return rc;
-  hipLaunchKernelGGL(k_bsdf_eval, dim3(g), dim3(256), 0, c->stream, c->ds, c->nmats, hits, wi, wo, n, info, out);
-  return shade_end(c);
+  return shade_call(c, "wr_bsdf_eval_dev", n, false,
+                    {wr::in(hits, recs(n, sizeof(wr_hit)), "hits"), wr::in(wi, recs(n, 12), "wi"),
+                     wr::in(wo, recs(n, 12), "wo"), wr::out(info, recs(n, sizeof(wr_bsdf_info)), "info", 1, true),
+                     wr::out(out, recs(n, sizeof(wr_bsdf_eval)), "out")}, [&](int g) {
+    hipLaunchKernelGGL(k_bsdf_eval, dim3(g), dim3(256), 0, c->stream, c->ds, c->nmats, hits, wi, wo, n, info, out);
+  });
 }
 
 int wr_bsdf_sample_dev(wr_context* c, const wr_hit* hits, const float* wi, const float* r3, int64_t n,
                        wr_bsdf_info* info, wr_bsdf_sample* out) {
-  int g;
-  if (int rc = shade_begin(c, "wr_bsdf_sample_dev", n, false,
-                           {{hits, sizeof(wr_hit), "hits", false, false}, {wi, 12, "wi", false, false},
-                            {r3, 12, "r3", false, false}, {info, sizeof(wr_bsdf_info), "info", true, true},
-                            {out, sizeof(wr_bsdf_sample), "out", true, false}}, &g))
-    return rc;
-  if (!g) return WR_OK;
-  DeviceGuard dg;
-  if (int rc = shade_order(c)) return rc;
-  hipLaunchKernelGGL(k_bsdf_sample, dim3(g), dim3(256), 0, c->stream, c->ds, c->nmats, hits, wi, r3, n, info, out);
-  return shade_end(c);
+  return shade_call(c, "wr_bsdf_sample_dev", n, false,
+                    {wr::in(hits, recs(n, sizeof(wr_hit)), "hits"), wr::in(wi, recs(n, 12), "wi"),
+                     wr::in(r3, recs(n, 12), "r3"), wr::out(info, recs(n, sizeof(wr_bsdf_info)), "info", 1, true),
+                     wr::out(out, recs(n, sizeof(wr_bsdf_sample)), "out")}, [&](int g) {
+    hipLaunchKernelGGL(k_bsdf_sample, dim3(g), dim3(256), 0, c->stream, c->ds, c->nmats, hits, wi, r3, n, info, out);
+  });
 }
 
 int wr_light_illuminate_dev(wr_context* c, const int32_t* light, const float* pos, const float* r3, int64_t n,
                             wr_light_illum* out) {
-  int g;
-  if (int rc = shade_begin(c, "wr_light_illuminate_dev", n, true,
-                           {{light, 4, "light", false, false}, {pos, 12, "pos", false, false},
-                            {r3, 12, "r3", false, false}, {out, sizeof(wr_light_illum), "out", true, false}}, &g))
-    return rc;
-  if (!g) return WR_OK;
-  DeviceGuard dg;
-  if (int rc = shade_order(c)) return rc;
-  hipLaunchKernelGGL(k_light_illuminate, dim3(g), dim3(256), 0, c->stream, c->ds, light, pos, r3, n, out);
-  return shade_end(c);
+  return shade_call(c, "wr_light_illuminate_dev", n, true,
+                    {wr::in(light, recs(n, 4), "light"), wr::in(pos, recs(n, 12), "pos"), wr::in(r3, recs(n, 12), "r3"),
+                     wr::out(out, recs(n, sizeof(wr_light_illum)), "out")}, [&](int g) {
+    hipLaunchKernelGGL(k_light_illuminate, dim3(g), dim3(256), 0, c->stream, c->ds, light, pos, r3, n, out);
+  });
 }
 
 int wr_light_emit_dev(wr_context* c, const int32_t* light, const float* dir_r3, const float* pos_r3, int64_t n,
                       wr_light_emission* out) {
-  int g;
-  if (int rc = shade_begin(c, "wr_light_emit_dev", n, true,
-                           {{light, 4, "light", false, false}, {dir_r3, 12, "dir_r3", false, false},
-                            {pos_r3, 12, "pos_r3", false, false},
-                            {out, sizeof(wr_light_emission), "out", true, false}}, &g))
-    return rc;
-  if (!g) return WR_OK;
-  DeviceGuard dg;
-  if (int rc = shade_order(c)) return rc;
-  hipLaunchKernelGGL(k_light_emit, dim3(g), dim3(256), 0, c->stream, c->ds, light, dir_r3, pos_r3, n, out);
-  return shade_end(c);
+  return shade_call(c, "wr_light_emit_dev", n, true,
+                    {wr::in(light, recs(n, 4), "light"), wr::in(dir_r3, recs(n, 12), "dir_r3"),
+                     wr::in(pos_r3, recs(n, 12), "pos_r3"), wr::out(out, recs(n, sizeof(wr_light_emission)), "out")},
+                    [&](int g) {
+    hipLaunchKernelGGL(k_light_emit, dim3(g), dim3(256), 0, c->stream, c->ds, light, dir_r3, pos_r3, n, out);
+  });
 }
 
 int wr_light_radiance_dev(wr_context* c, const wr_hit* hits, const float* ray_d, int64_t n, wr_light_rad* out) {
-  int g;
-  if (int rc = shade_begin(c, "wr_light_radiance_dev", n, true,
-                           {{hits, sizeof(wr_hit), "hits", false, false}, {ray_d, 12, "ray_d", false, false},
-                            {out, sizeof(wr_light_rad), "out", true, false}}, &g))
-    return rc;
-  if (!g) return WR_OK;
-  DeviceGuard dg;
-  if (int rc = shade_order(c)) return rc;
-  hipLaunchKernelGGL(k_light_radiance, dim3(g), dim3(256), 0, c->stream, c->ds, hits, ray_d, n, out);
-  return shade_end(c);
+  return shade_call(c, "wr_light_radiance_dev", n, true,
+                    {wr::in(hits, recs(n, sizeof(wr_hit)), "hits"), wr::in(ray_d, recs(n, 12), "ray_d"),
+                     wr::out(out, recs(n, sizeof(wr_light_rad)), "out")}, [&](int g) {
+    hipLaunchKernelGGL(k_light_radiance, dim3(g), dim3(256), 0, c->stream, c->ds, hits, ray_d, n, out);
+  });
 }
 
 int wr_rng_uniform_dev(wr_context* c, uint32_t seed, uint32_t iteration, uint32_t subpath, const uint32_t* path,
                        uint32_t* ctr, int32_t draws, int64_t n, float* out) {
   if (c && (draws < 1 || draws > 64)) return fail(WR_E_ARG, "wr_rng_uniform_dev: draws must be 1..64");
-  int g;
-  if (int rc = shade_begin(c, "wr_rng_uniform_dev", n, false,
-                           {{path, 4, "path", false, true}, {ctr, 4, "ctr", true, true},
-                            {out, 4 * static_cast<size_t>(draws), "out", true, false}}, &g))
-    return rc;
-  if (!g) return WR_OK;
-  DeviceGuard dg;
-  if (int rc = shade_order(c)) return rc;
-  hipLaunchKernelGGL(k_rng_uniform, dim3(g), dim3(256), 0, c->stream, seed, iteration, subpath, path, ctr, draws, n,
-                     out);
-  return shade_end(c);
+  return shade_call(c, "wr_rng_uniform_dev", n, false,
+                    {wr::in(path, recs(n, 4), "path", 1, true), wr::out(ctr, recs(n, 4), "ctr", 1, true),
+                     wr::out(out, recs(n, 4 * static_cast<size_t>(draws)), "out")}, [&](int g) {
+    hipLaunchKernelGGL(k_rng_uniform, dim3(g), dim3(256), 0, c->stream, seed, iteration, subpath, path, ctr, draws, n,
+                       out);
+  });
 }
 
 // ---- point sets on the device (wr_points_*; kernels in
 // wr_points.h).  Arguments are checked like those of the shading calls; what
 // the arrays hold (offsets, radii, coordinates) is checked by the kernels.
-struct PtsArg {
-  const void* p;
-  size_t bytes;
-  size_t align;
-  const char* name;
-  bool out;
-  bool optional;
-};
 // the bucket count of n points: 2^k, at least twice the points and one row run
 static uint32_t pts_table(int64_t n) {
   uint32_t t = kPtsRowW;
   while (static_cast<int64_t>(t) < 2 * n) t <<= 1;
   return t;
 }
-// WR_OK and *go = false: nothing to do (nq == 0)
-static int pts_begin(wr_context* c, const wr_points* idx, const char* call, int64_t nq,
-                     std::initializer_list<PtsArg> args, bool* go) {
-  *go = false;
+// The frame of a query call: the scalars and the arrays checked, then launch()
+// on the context stream between api_order and api_finish.
+static int pts_call(wr_context* c, const wr_points* idx, const char* call, int64_t nq,
+                    std::initializer_list<wr::Arg> args, const std::function<void()>& launch) {
   const std::string who = std::string(call) + ": ";
   if (!c) return fail(WR_E_ARG, who + "null context");
   if (nq < 0) return fail(WR_E_ARG, who + "nq < 0");
@@ -3793,21 +3718,11 @@ static int pts_begin(wr_context* c, const wr_points* idx, const char* call, int6
   if (idx->ctx != c) return fail(WR_E_ARG, who + "the index belongs to another context");
   if (nq > (int64_t(1) << 28)) return fail(WR_E_ARG, who + "at most 2^28 queries per call");
   if (nq == 0) return WR_OK;
-  for (const PtsArg& a : args) {
-    if (!a.p && a.bytes && !a.optional) return fail(WR_E_ARG, who + "null " + a.name);
-    if (a.p && reinterpret_cast<uintptr_t>(a.p) % a.align)
-      return fail(WR_E_ARG, who + a.name + " must be " + std::to_string(a.align) + "-byte aligned");
-  }
-  for (const PtsArg& a : args)
-    if (a.p && a.bytes)
-      if (int rc = check_dev_range(c, a.p, a.bytes, (who + a.name).c_str(), "no point-set call: copy it to the device"))
-        return rc;
-  for (const PtsArg& a : args)
-    for (const PtsArg& b : args)
-      if (&a < &b && (a.out || b.out) && a.bytes && b.bytes && ranges_overlap(a.p, a.bytes, b.p, b.bytes))
-        return fail(WR_E_ARG, who + a.name + " overlaps " + b.name);
-  *go = true;
-  return WR_OK;
+  if (int rc = check_dev_args(c, call, args, "no point-set call: copy it to the device")) return rc;
+  DeviceGuard dg;
+  if (int rc = api_order(c)) return rc;
+  launch();
+  return api_finish(c);
 }
 
 int wr_points_build_dev(wr_context* c, const float* pos, int64_t n, float cell, wr_points** out) {
@@ -3818,14 +3733,12 @@ int wr_points_build_dev(wr_context* c, const float* pos, int64_t n, float cell, 
   *out = nullptr;
   if (n > (int64_t(1) << 28)) return fail(WR_E_ARG, who + "at most 2^28 points");
   if (!(cell > 0.f) || !std::isfinite(cell)) return fail(WR_E_ARG, who + "cell must be a finite number > 0");
-  if (n && !pos) return fail(WR_E_ARG, who + "null pos");
-  if (n && reinterpret_cast<uintptr_t>(pos) % 4) return fail(WR_E_ARG, who + "pos must be 4-byte aligned");
-  if (n)
-    if (int rc = check_dev_range(c, pos, static_cast<size_t>(n) * 12, (who + "pos").c_str(),
-                                 "no point-set call: copy it to the device"))
+  if (n)  // (no points: pos is not looked at)
+    if (int rc = check_dev_args(c, "wr_points_build_dev", {wr::in(pos, recs(n, 12), "pos", 4)},
+                                "no point-set call: copy it to the device"))
       return rc;
   DeviceGuard dg;
-  if (int rc = shade_order(c)) return rc;
+  if (int rc = api_order(c)) return rc;
   const hipStream_t sm = c->stream;
   const int ni = static_cast<int>(n);
   const uint32_t T = pts_table(n);
@@ -3926,37 +3839,31 @@ static int pts_radius_call(wr_context* c, const wr_points* idx, const char* call
     if (fill && capacity > (int64_t(1) << 40)) return fail(WR_E_ARG, who + "capacity above 2^40");
   }
   const size_t nb = nq > 0 ? static_cast<size_t>(nq) : 0, cb = capacity > 0 ? static_cast<size_t>(capacity) : 0;
-  bool go;
-  int rc;
-  if (fill)
-    rc = pts_begin(c, idx, call, nq,
-                   {{q, nb * 12, 4, "q", false, false}, {radii, nb * 4, 4, "radii", false, true},
-                    {offset, (nb + 1) * 8, 8, "offset", false, false}, {index, cb * 4, 4, "index", true, false}}, &go);
-  else
-    rc = pts_begin(c, idx, call, nq,
-                   {{q, nb * 12, 4, "q", false, false}, {radii, nb * 4, 4, "radii", false, true},
-                    {count, nb * 4, 4, "count", true, false}}, &go);
-  if (rc || !go) return rc;
-  DeviceGuard dg;
-  if (int r2 = shade_order(c)) return r2;
+  const wr::Arg in_q = wr::in(q, nb * 12, "q", 4), in_radii = wr::in(radii, nb * 4, "radii", 4, true);
+  const auto launch = [&] {
 #if WR_PTS_RADIUS_WAVE  // a wave per query (the faster of the two forms, profiles/r18/points)
-  const int g = static_cast<int>((nq + 3) / 4);
-  if (fill)
-    hipLaunchKernelGGL(k_pts_radius_wave<true>, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, radius, radii, offset,
-                       capacity, static_cast<int32_t*>(nullptr), index);
-  else
-    hipLaunchKernelGGL(k_pts_radius_wave<false>, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, radius, radii,
-                       static_cast<const int64_t*>(nullptr), int64_t(0), count, static_cast<int32_t*>(nullptr));
+    const int g = static_cast<int>((nq + 3) / 4);
+    if (fill)
+      hipLaunchKernelGGL(k_pts_radius_wave<true>, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, radius, radii,
+                         offset, capacity, static_cast<int32_t*>(nullptr), index);
+    else
+      hipLaunchKernelGGL(k_pts_radius_wave<false>, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, radius, radii,
+                         static_cast<const int64_t*>(nullptr), int64_t(0), count, static_cast<int32_t*>(nullptr));
 #else  // a lane per query
-  const int g = static_cast<int>((nq + 255) / 256);
-  if (fill)
-    hipLaunchKernelGGL(k_pts_radius<true>, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, radius, radii, offset,
-                       capacity, static_cast<int32_t*>(nullptr), index);
-  else
-    hipLaunchKernelGGL(k_pts_radius<false>, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, radius, radii,
-                       static_cast<const int64_t*>(nullptr), int64_t(0), count, static_cast<int32_t*>(nullptr));
+    const int g = static_cast<int>((nq + 255) / 256);
+    if (fill)
+      hipLaunchKernelGGL(k_pts_radius<true>, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, radius, radii, offset,
+                         capacity, static_cast<int32_t*>(nullptr), index);
+    else
+      hipLaunchKernelGGL(k_pts_radius<false>, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, radius, radii,
+                         static_cast<const int64_t*>(nullptr), int64_t(0), count, static_cast<int32_t*>(nullptr));
 #endif
-  return shade_end(c);
+  };
+  if (fill)
+    return pts_call(c, idx, call, nq,
+                    {in_q, in_radii, wr::in(offset, (nb + 1) * 8, "offset", 8), wr::out(index, cb * 4, "index", 4)},
+                    launch);
+  return pts_call(c, idx, call, nq, {in_q, in_radii, wr::out(count, nb * 4, "count", 4)}, launch);
 }
 
 int wr_points_count_dev(wr_context* c, const wr_points* idx, const float* q, int64_t nq, float radius,
@@ -3978,18 +3885,14 @@ int wr_points_knn_dev(wr_context* c, const wr_points* idx, const float* q, int64
     if (!(max_sqr_dist >= 0.f)) return fail(WR_E_ARG, who + "max_sqr_dist must not be negative or NaN");
   }
   const size_t nb = nq > 0 ? static_cast<size_t>(nq) : 0, kb = nb * static_cast<size_t>(k > 0 ? k : 0) * 4;
-  bool go;
-  if (int rc = pts_begin(c, idx, "wr_points_knn_dev", nq,
-                         {{q, nb * 12, 4, "q", false, false}, {index, kb, 4, "index", true, false},
-                          {sqr_dist, kb, 4, "sqr_dist", true, false}, {count, nb * 4, 4, "count", true, false}}, &go))
-    return rc;
-  if (!go) return WR_OK;
-  DeviceGuard dg;
-  if (int rc = shade_order(c)) return rc;
-  const int g = static_cast<int>((nq + 3) / 4);  // a wave per query
-  hipLaunchKernelGGL(k_pts_knn, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, k, max_sqr_dist, index, sqr_dist,
-                     count);
-  return shade_end(c);
+  return pts_call(c, idx, "wr_points_knn_dev", nq,
+                  {wr::in(q, nb * 12, "q", 4), wr::out(index, kb, "index", 4), wr::out(sqr_dist, kb, "sqr_dist", 4),
+                   wr::out(count, nb * 4, "count", 4)},
+                  [&] {
+    const int g = static_cast<int>((nq + 3) / 4);  // a wave per query
+    hipLaunchKernelGGL(k_pts_knn, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, k, max_sqr_dist, index, sqr_dist,
+                       count);
+  });
 }
 
 int wr_create_multi(const wr_scene* sc, const int* devices, int n, wr_context** out) {
@@ -4089,10 +3992,7 @@ int wr_film_reduce(wr_context* c, float* film, int64_t nfloat, int root) {
   if (!c->comm) return fail(WR_E_ARG, "no communicator: call wr_comm_init first");
   if (root < 0 || root >= c->comm_ranks) return fail(WR_E_ARG, "bad root rank");
   DeviceGuard dg;
-  HIPCHK(hipSetDevice(c->device));
-  // ordered after the caller's work on the legacy null stream, like a render
-  (void)hipEventRecord(c->t_null, nullptr);
-  (void)hipStreamWaitEvent(c->stream, c->t_null, 0);
+  if (int rc = api_order(c)) return rc;
   NCCLCHK(rccl().reduce(film, film, static_cast<size_t>(nfloat), ncclFloat32, ncclSum, root, c->comm, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return WR_OK;
