@@ -234,8 +234,13 @@ struct BdptBuf {
   int* cidx;
   int vcap = 0, ccap = 0;
   // extension-ray queues (double buffered, SoA with stride qs).  Overlapped
-  // schedule: qs = 2P, the light pass's rays of a bounce first (count
-  // ext[b]), the camera pass's behind them (count ext[kCamSlot + b])
+  // schedule: the light pass's rays of a bounce first (count ext[b]), the
+  // camera pass's behind them (count ext[kCamSlot + b]).
+  // qs: the plane stride of the ray arrays the traversal reads, q_o / q_d and
+  // in BDPT sq[].o / sq[].d as well: there they and q_t, q_prim, sq[].t,
+  // sq[].prim are segments of the pipeline's ray slab (wr_queue_slab.h) and qs
+  // is the slab's entries.  VertexCM: arrays of the set's own, qs = P, and
+  // sq[].o / sq[].d keep the stride cap_sq
   int qs = 0;
   float *q_o[2], *q_d[2], *q_t[2];
   int *q_path[2], *q_prim[2];
@@ -489,8 +494,8 @@ __device__ __forceinline__ void queue_connection(const BdptArgs& A, int qslot, b
   const int cap = B.cap_sq;
   const int si = wave_append(&A.sc->sq[qslot], shoot);
   if (sq_fits(A, shoot, si)) {
-    st3(Q.o, cap, si, hp);
-    st3(Q.d, cap, si, sdir);
+    st3(Q.o, B.qs, si, hp);  // (o, d: segments of the ray slab, plane stride qs)
+    st3(Q.d, B.qs, si, sdir);
     Q.cut[si] = occl_cut(hp, stgt, dot(stgt - hp, sdir));
     if (counted) {
       st3(Q.tgt, cap, si, stgt);
@@ -751,8 +756,8 @@ __device__ __forceinline__ void light_vertex(const BdptArgs& A, const DMat* mats
   const int si = wave_append(&A.sc->sq[sslot], splat);
   if (sq_fits(A, splat, si)) {
     const BdptBuf::Sq& Q = B.sq[sslot & 1];
-    st3(Q.o, B.cap_sq, si, s_o);
-    st3(Q.d, B.cap_sq, si, s_d);
+    st3(Q.o, B.qs, si, s_o);
+    st3(Q.d, B.qs, si, s_d);
     st3(Q.tgt, B.cap_sq, si, S.cam.pos);
     st3(Q.val, B.cap_sq, si, s_val);
     Q.cut[si] = occl_cut(s_o, S.cam.pos, dot(S.cam.pos - s_o, s_d));
@@ -1056,8 +1061,8 @@ __device__ __forceinline__ void camera_vertex(const BdptArgs& A, const DMat* mat
   {
     const int ni = wave_append(&A.sc->sq[oslot], nee);
     if (sq_fits(A, nee, ni)) {
-      st3(Q.o, cap, ni, hp);
-      st3(Q.d, cap, ni, nee_d);
+      st3(Q.o, B.qs, ni, hp);
+      st3(Q.d, B.qs, ni, nee_d);
       st3(Q.tgt, cap, ni, nee_tgt);
       Q.cut[ni] = occl_cut(hp, nee_tgt, dot(nee_tgt - hp, nee_d));
       Q.meta[ni] = (SQ_NEE << 30) | p;
@@ -1065,8 +1070,8 @@ __device__ __forceinline__ void camera_vertex(const BdptArgs& A, const DMat* mat
     }
     const int bi = wave_append(&A.sc->sq[oslot], dib);
     if (sq_fits(A, dib, bi)) {
-      st3(Q.o, cap, bi, dib_o);
-      st3(Q.d, cap, bi, dib_d);
+      st3(Q.o, B.qs, bi, dib_o);
+      st3(Q.d, B.qs, bi, dib_d);
       Q.cut[bi] = -WR_INF;  // needs the closest hit (same light?)
       Q.meta[bi] = (SQ_DIB << 30) | p;
       Q.pix[bi] = pix;
@@ -1129,12 +1134,16 @@ __device__ __forceinline__ void camera_shade_body(const BdptArgs& A, const DMat*
 // traversal.  A DI record is finalized (getDirectIllumination's combination,
 // :533-607) by whichever of its rays is resolved last: each resolve adds
 // (its result bit - 1) to the record's state word in one atomic.
+// VCM: the queue's o / d are arrays of its own with the stride cap_sq (wr_vcm.h);
+// BDPT's are segments of the pipeline's ray slab with the plane stride qs
+template <bool VCM = false>
 __device__ __forceinline__ void sq_resolve_body(const BdptArgs& A, int slot, int bid, int nblk) {
   const BdptBuf& B = A.B;
   const DevScene& S = A.S;
   const BdptBuf::Sq& Q = B.sq[slot & 1];
   const BdptBuf::Di& D = B.di[slot & 1];
   const int cap = B.cap_sq, n = min(A.sc->sq[slot], cap);  // (appends past cap were dropped: overflow)
+  const int rs = VCM ? cap : B.qs;
   const int gstride = nblk * blockDim.x;
   const int nround = (n + gstride - 1) / gstride * gstride;
   for (int j = bid * blockDim.x + threadIdx.x; j < nround; j += gstride) {
@@ -1159,12 +1168,12 @@ __device__ __forceinline__ void sq_resolve_body(const BdptArgs& A, int slot, int
         is_shadow = true;
         bool unocc = true;
         if (prim >= 0) {
-          const V3 o = ld3(Q.o, cap, j), d = ld3(Q.d, cap, j);
+          const V3 o = ld3(Q.o, rs, j), d = ld3(Q.d, rs, j);
           unocc = near_eq(o + d * t, ld3(Q.tgt, cap, j));
         }
 #ifdef WR_DEBUG_PATH
         if (kind == SQ_SPLAT && A.base + p == WR_DEBUG_PATH && A.iter == WR_DEBUG_ITER) {
-          const V3 o = ld3(Q.o, cap, j), d = ld3(Q.d, cap, j), v = ld3(Q.val, cap, j);
+          const V3 o = ld3(Q.o, rs, j), d = ld3(Q.d, rs, j), v = ld3(Q.val, cap, j);
           printf("[dbg gpu] splat o %a %a %a d %a %a %a prim %d t %a unocc %d val %a %a %a pix %d\n", o.x, o.y, o.z, d.x,
                  d.y, d.z, prim, t, (int)unocc, v.x, v.y, v.z, Q.pix[j]);
         }

@@ -1314,7 +1314,7 @@ struct QueueIndex {
     for (int i = 0; i < kMaxQueues; ++i) {
       // (a shadow queue's count may pass its capacity: the appends past it were
       // dropped and the render is redone, BdptBuf)
-      if (i < Q.n && Q.q[i].count) acc += min(*Q.q[i].count + (Q.q[i].count2 ? *Q.q[i].count2 : 0), Q.q[i].cap);
+      if (i < Q.n && Q.q[i].count) acc += min(*Q.q[i].count + (Q.q[i].count2 ? *Q.q[i].count2 : 0), Q.lim[i]);
       qend[i] = acc;
     }
     n = acc;
@@ -1331,6 +1331,47 @@ struct QueueIndex {
     r = idx - q0;
   }
 };
+// The slab form's index (SlabQueues): the same numbering, and the ray's slab
+// entry e = idx + shift[q] - qend[q - 1].  The offset is wave-uniform per
+// queue and computed once; a lane adds the steps of the queue ends it has
+// passed -- the same three compares, then every access is base[e],
+// base[stride + e], base[2 * stride + e] with no pointer selected per lane.
+// (Sums of steps, not a select among per-queue offsets: the compiler turns
+// that select into a dynamically indexed array, which lands in scratch.)
+struct SlabIndex {
+  int qend[kMaxQueues];
+  int step[kMaxQueues];  // step[0]: queue 0's offset; step[i]: queue i's offset less queue i - 1's
+  int n;
+  __device__ __forceinline__ explicit SlabIndex(const SlabQueues& Q) {
+    int acc = 0, prev = 0;
+#pragma unroll
+    for (int i = 0; i < kMaxQueues; ++i) {
+      const int rel = Q.shift[i] - acc;
+      step[i] = rel - prev;
+      prev = rel;
+      if (i < Q.n && Q.count[i]) acc += min(*Q.count[i] + (Q.count2[i] ? *Q.count2[i] : 0), Q.lim[i]);
+      qend[i] = acc;
+    }
+    n = acc;
+  }
+  // the slab entry of launch index idx < n
+  __device__ __forceinline__ int entry(int idx) const {
+    int e = idx + step[0];
+#pragma unroll
+    for (int i = 0; i < kMaxQueues - 1; ++i) e += idx >= qend[i] ? step[i + 1] : 0;
+    return e;
+  }
+};
+template <class QT>
+struct queue_index {
+  using type = QueueIndex;
+};
+template <>
+struct queue_index<SlabQueues> {
+  using type = SlabIndex;
+};
+template <class QT>
+constexpr bool kIsSlab = std::is_same_v<QT, SlabQueues>;
 #ifndef WR_QFIELD_SGPR
 #define WR_QFIELD_SGPR 1
 #endif
@@ -1471,8 +1512,10 @@ __device__ __forceinline__ bool first_cells_crossed(const FastScene& F, int p1, 
 // cells) are listed by launch index in rlist for k_fast_resolve, which then
 // reads those rays only.  The test is the resolve's own, on the same floats,
 // and runs in full waves over the settle buffer (settle_batch below).
-template <bool COUNT, int W, bool SPH, bool RL = false>
-__device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F, const TraceQueues& Q, int* fetch,
+// QT: the launch's queues in the general form (TraceQueues) or as segments of
+// one ray slab (SlabQueues); the slab form holds the ray's slab entry in r
+template <bool COUNT, int W, bool SPH, bool RL = false, class QT = TraceQueues>
+__device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F, const QT& Q, int* fetch,
                                            float* t2buf, int2* pairs, int2* spill, uint32_t* smem, FastCounters& ctr,
                                            int wgid, int nwg,  // this workgroup's index among the launch's nwg
                                            int* rlist = nullptr, int* rlist_n = nullptr) {
@@ -1492,7 +1535,8 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
   int* stk_link = reinterpret_cast<int*>(lds) + lane;
   uint16_t* stk_t = reinterpret_cast<uint16_t*>(reinterpret_cast<int*>(lds) + min(F.sdepth, kLdsStack) * 64) + lane;
   const size_t gl = static_cast<size_t>(nblk) * 64, gidx = static_cast<size_t>(bid) * 64 + lane;
-  const QueueIndex QI(Q);
+  constexpr bool kSlab = kIsSlab<QT>;
+  const typename queue_index<QT>::type QI(Q);
   const int n = QI.n;
   // Waves past the ones the rays need leave before touching the shared cursor:
   // the first reservations cover every index, and a launch of few rays (a
@@ -1573,15 +1617,23 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
     if (lane < m) {
       const int2 e = sbuf[lane];
       sidx = e.x;
-      int sq = 0, sr = 0;
-      QI.locate(sidx, sq, sr);
-      const float* o3 = qfield(Q, sq, [](const RayQueue& x) { return x.o3; });
-      const float* d3 = qfield(Q, sq, [](const RayQueue& x) { return x.d3; });
-      const int cap = qfield(Q, sq, [](const RayQueue& x) { return x.cap; });
-      const float* tmx = qfield(Q, sq, [](const RayQueue& x) { return x.tmax; });
-      const V3 so = v3(o3[sr], o3[cap + sr], o3[2 * cap + sr]);
-      const V3 sd = v3(d3[sr], d3[cap + sr], d3[2 * cap + sr]);
-      const float stmax = tmx ? tmx[sr] : WR_INF;
+      V3 so, sd;
+      float stmax = WR_INF;
+      if constexpr (kSlab) {
+        const int se = QI.entry(sidx), cap = Q.stride;
+        so = v3(Q.o3[se], Q.o3[cap + se], Q.o3[2 * cap + se]);
+        sd = v3(Q.d3[se], Q.d3[cap + se], Q.d3[2 * cap + se]);
+      } else {
+        int sq = 0, sr = 0;
+        QI.locate(sidx, sq, sr);
+        const float* o3 = qfield(Q, sq, [](const RayQueue& x) { return x.o3; });
+        const float* d3 = qfield(Q, sq, [](const RayQueue& x) { return x.d3; });
+        const int cap = qfield(Q, sq, [](const RayQueue& x) { return x.cap; });
+        const float* tmx = qfield(Q, sq, [](const RayQueue& x) { return x.tmax; });
+        so = v3(o3[sr], o3[cap + sr], o3[2 * cap + sr]);
+        sd = v3(d3[sr], d3[cap + sr], d3[2 * cap + sr]);
+        stmax = tmx ? tmx[sr] : WR_INF;
+      }
       const V3 sbinv = v3(clamp_inv(sd.x), clamp_inv(sd.y), clamp_inv(sd.z));
       unproven = !first_cells_crossed(F, e.y, so, sd, sbinv, stmax);
     }
@@ -1677,16 +1729,25 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
         const bool take = idle && idx < n;
         if (take) {
           lidx = idx;
-          QI.locate(idx, qi, r);
-          const float* o3 = qfield(Q, qi, [](const RayQueue& x) { return x.o3; });
-          const float* d3 = qfield(Q, qi, [](const RayQueue& x) { return x.d3; });
-          const int cap = qfield(Q, qi, [](const RayQueue& x) { return x.cap; });
-          const float* tmn = qfield(Q, qi, [](const RayQueue& x) { return x.tmin; });
-          const float* tmx = qfield(Q, qi, [](const RayQueue& x) { return x.tmax; });
-          o = v3(o3[r], o3[cap + r], o3[2 * cap + r]);
-          d = v3(d3[r], d3[cap + r], d3[2 * cap + r]);
-          rtmin = tmn ? tmn[r] : 0.f;
-          rtmax = tmx ? tmx[r] : WR_INF;
+          if constexpr (kSlab) {
+            r = QI.entry(idx);
+            const int cap = Q.stride;
+            o = v3(Q.o3[r], Q.o3[cap + r], Q.o3[2 * cap + r]);
+            d = v3(Q.d3[r], Q.d3[cap + r], Q.d3[2 * cap + r]);
+            rtmin = 0.f;
+            rtmax = WR_INF;
+          } else {
+            QI.locate(idx, qi, r);
+            const float* o3 = qfield(Q, qi, [](const RayQueue& x) { return x.o3; });
+            const float* d3 = qfield(Q, qi, [](const RayQueue& x) { return x.d3; });
+            const int cap = qfield(Q, qi, [](const RayQueue& x) { return x.cap; });
+            const float* tmn = qfield(Q, qi, [](const RayQueue& x) { return x.tmin; });
+            const float* tmx = qfield(Q, qi, [](const RayQueue& x) { return x.tmax; });
+            o = v3(o3[r], o3[cap + r], o3[2 * cap + r]);
+            d = v3(d3[r], d3[cap + r], d3[2 * cap + r]);
+            rtmin = tmn ? tmn[r] : 0.f;
+            rtmax = tmx ? tmx[r] : WR_INF;
+          }
           binv = v3(clamp_inv(d.x), clamp_inv(d.y), clamp_inv(d.z));
           dlen = sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
           if (!(dlen > 0.f)) dlen = 1.f;
@@ -2020,8 +2081,13 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
         pairs[lidx] = two ? make_int2(p2, __float_as_int(t2)) : make_int2(-1, 0);
       }
       if (gz) po = po >= 0 ? (po | kGrazeMark) : kGrazeMiss;
-      qfield(Q, qi, [](const RayQueue& x) { return x.out_t; })[r] = p1 >= 0 ? t1 : WR_INF;
-      qfield(Q, qi, [](const RayQueue& x) { return x.out_prim; })[r] = po;
+      if constexpr (kSlab) {
+        Q.out_t[r] = p1 >= 0 ? t1 : WR_INF;
+        Q.out_prim[r] = po;
+      } else {
+        qfield(Q, qi, [](const RayQueue& x) { return x.out_t; })[r] = p1 >= 0 ? t1 : WR_INF;
+        qfield(Q, qi, [](const RayQueue& x) { return x.out_prim; })[r] = po;
+      }
       if constexpr (RL) {
         listed = po != p1;             // marked: a near-tie or a grazing ray
         queued = !listed && p1 >= 0;   // an unmarked hit: the settle buffer (a miss is settled)
@@ -2053,13 +2119,14 @@ constexpr int kTieEntry = 1 << 29;
 // The rare rays it cannot settle (near-ties, t1 not reached) go to `hard` for
 // k_fast_hard, so that their register-hungry code does not lower this
 // kernel's occupancy.
-template <bool COUNT>
-__device__ __forceinline__ void resolve_fast(const DevScene& S, const FastScene& F, const TraceQueues& Q,
+template <bool COUNT, class QT = TraceQueues>
+__device__ __forceinline__ void resolve_fast(const DevScene& S, const FastScene& F, const QT& Q,
                                              const float* t2buf, int* hard, int* hard_n, int hcap,
                                              FastCounters& ctr, const int* rlist = nullptr,
                                              const int* rlist_n = nullptr) {
   const int lane = __lane_id();
-  const QueueIndex QI(Q);
+  constexpr bool kSlab = kIsSlab<QT>;
+  const typename queue_index<QT>::type QI(Q);
   // the search's list (RL), or every ray of the launch
   const int nr = rlist ? min(*rlist_n, QI.n) : QI.n;
   // the capacity diagnostics (wrong answers, never valid indices): the rays a
@@ -2068,8 +2135,14 @@ __device__ __forceinline__ void resolve_fast(const DevScene& S, const FastScene&
   if (F.diag & 16) {
     for (int idx = blockIdx.x * 64 + lane; idx < QI.n; idx += gridDim.x * 64) {
       int q = 0, r = 0;
-      QI.locate(idx, q, r);
-      int* op = qfield(Q, q, [](const RayQueue& x) { return x.out_prim; });
+      int* op;
+      if constexpr (kSlab) {
+        r = QI.entry(idx);
+        op = Q.out_prim;
+      } else {
+        QI.locate(idx, q, r);
+        op = qfield(Q, q, [](const RayQueue& x) { return x.out_prim; });
+      }
       op[r] = unmark(op[r]);
     }
     return;
@@ -2081,19 +2154,34 @@ __device__ __forceinline__ void resolve_fast(const DevScene& S, const FastScene&
     int q = 0, r = 0, p1 = -1;
     float t1 = WR_INF;
     if (idx < QI.n) {
-      QI.locate(idx, q, r);
       // every load that does not depend on p1 in flight at once
-      const int pm = qfield(Q, q, [](const RayQueue& x) { return x.out_prim; })[r];
-      p1 = unmark(pm);
-      t1 = qfield(Q, q, [](const RayQueue& x) { return x.out_t; })[r];
-      const float t2 = F.diag ? t2buf[idx] : 0.f;
-      const float* o3 = qfield(Q, q, [](const RayQueue& x) { return x.o3; });
-      const float* d3 = qfield(Q, q, [](const RayQueue& x) { return x.d3; });
-      const int cap = qfield(Q, q, [](const RayQueue& x) { return x.cap; });
-      const float* tmx = qfield(Q, q, [](const RayQueue& x) { return x.tmax; });
-      const V3 o = v3(o3[r], o3[cap + r], o3[2 * cap + r]);
-      const V3 d = v3(d3[r], d3[cap + r], d3[2 * cap + r]);
-      const float rtmax = tmx ? tmx[r] : WR_INF;
+      int pm;
+      float t2;
+      V3 o, d;
+      float rtmax = WR_INF;
+      if constexpr (kSlab) {
+        r = QI.entry(idx);
+        const int cap = Q.stride;
+        pm = Q.out_prim[r];
+        p1 = unmark(pm);
+        t1 = Q.out_t[r];
+        t2 = F.diag ? t2buf[idx] : 0.f;
+        o = v3(Q.o3[r], Q.o3[cap + r], Q.o3[2 * cap + r]);
+        d = v3(Q.d3[r], Q.d3[cap + r], Q.d3[2 * cap + r]);
+      } else {
+        QI.locate(idx, q, r);
+        pm = qfield(Q, q, [](const RayQueue& x) { return x.out_prim; })[r];
+        p1 = unmark(pm);
+        t1 = qfield(Q, q, [](const RayQueue& x) { return x.out_t; })[r];
+        t2 = F.diag ? t2buf[idx] : 0.f;
+        const float* o3 = qfield(Q, q, [](const RayQueue& x) { return x.o3; });
+        const float* d3 = qfield(Q, q, [](const RayQueue& x) { return x.d3; });
+        const int cap = qfield(Q, q, [](const RayQueue& x) { return x.cap; });
+        const float* tmx = qfield(Q, q, [](const RayQueue& x) { return x.tmax; });
+        o = v3(o3[r], o3[cap + r], o3[2 * cap + r]);
+        d = v3(d3[r], d3[cap + r], d3[2 * cap + r]);
+        rtmax = tmx ? tmx[r] : WR_INF;
+      }
       // p1's membership record: one line with its first four leaves' cells
       const float4* pr = F.prim_rec + 8 * static_cast<size_t>(max(p1, 0));
       const float4 c0 = pr[0], c1 = pr[1], c2 = pr[2], c3 = pr[3], c4 = pr[4], c5 = pr[5];
@@ -2148,7 +2236,8 @@ __device__ __forceinline__ void resolve_fast(const DevScene& S, const FastScene&
       }
     }
     if ((need && (F.diag & (32 | 128))) || (scan && (F.diag & (32 | 64)))) {  // (diagnostics, as above)
-      qfield(Q, q, [](const RayQueue& x) { return x.out_prim; })[r] = p1;
+      if constexpr (kSlab) Q.out_prim[r] = p1;
+      else qfield(Q, q, [](const RayQueue& x) { return x.out_prim; })[r] = p1;
       need = scan = false;
     }
     const int slot = fast_append(hard_n, need);
@@ -2268,6 +2357,22 @@ struct ListedRay {
   int2 pair;  // near-ties: the search's second hit (p2, t2 bits) when its first window holds two, else (-1, 0)
 };
 
+// (slab form: r is the ray's slab entry, the arrays the launch's own)
+__device__ __forceinline__ ListedRay listed_ray(const SlabQueues& Q, const SlabIndex& QI, int idx) {
+  ListedRay L;
+  const int r = L.r = QI.entry(idx), cap = Q.stride;
+  L.outp = Q.out_prim;
+  L.outt = Q.out_t;
+  L.t1 = L.outt[r];
+  L.p1 = unmark(L.outp[r]);
+  L.o = v3(Q.o3[r], Q.o3[cap + r], Q.o3[2 * cap + r]);
+  L.d = v3(Q.d3[r], Q.d3[cap + r], Q.d3[2 * cap + r]);
+  L.rtmin = 0.f;
+  L.rtmax = WR_INF;
+  L.walk = false;
+  L.pair = make_int2(-1, 0);
+  return L;
+}
 __device__ __forceinline__ ListedRay listed_ray(const TraceQueues& Q, const QueueIndex& QI, int idx) {
   ListedRay L;
   int q;
@@ -2334,11 +2439,11 @@ __device__ __forceinline__ void hard_rays(const DevScene& S, const FastScene& F,
     }
   }
 }
-template <bool COUNT, bool WAVE>
-__device__ __forceinline__ void hard_fast(const DevScene& S, const FastScene& F, const TraceQueues& Q,
+template <bool COUNT, bool WAVE, class QT = TraceQueues>
+__device__ __forceinline__ void hard_fast(const DevScene& S, const FastScene& F, const QT& Q,
                                           const int* hard, const int* hard_n, const int2* pairs, int bid, int nb,
                                           uint32_t* lds, FastCounters& ctr) {
-  const QueueIndex QI(Q);
+  const typename queue_index<QT>::type QI(Q);
   const int nh = (F.diag & (32 | 128)) ? 0 : hard_n[0];
   hard_rays<COUNT, WAVE>(S, F, nh, [&](int i) {
     const int e = hard[i];
@@ -2357,11 +2462,11 @@ __device__ __forceinline__ void hard_fast(const DevScene& S, const FastScene& F,
 // at one iteration's early steps those waves outnumber the slots the hard
 // kernel's registers leave).  A ray the lane cannot settle (a walk) is
 // resolved by its whole wave afterwards (hard_rays).
-template <bool COUNT>
-__device__ __forceinline__ void pair_fast(const DevScene& S, const FastScene& F, const TraceQueues& Q,
+template <bool COUNT, class QT = TraceQueues>
+__device__ __forceinline__ void pair_fast(const DevScene& S, const FastScene& F, const QT& Q,
                                           const int* plist, const int* hard_n, const int2* pairs, int bid, int nb,
                                           uint32_t* lds, FastCounters& ctr) {
-  const QueueIndex QI(Q);
+  const typename queue_index<QT>::type QI(Q);
   const int np = hard_n[2];
   hard_rays<COUNT, false>(S, F, np, [&](int i) {
     const int idx = plist[i];
@@ -2376,14 +2481,14 @@ __device__ __forceinline__ void pair_fast(const DevScene& S, const FastScene& F,
 // leaf's cell, else the replay of its path -- and stop once one is reached;
 // p1 then stands.  If none is, t1's triangle is not visited and the ray is
 // settled in general by the same wave (settle_ray, one ray per wave).
-template <bool COUNT>
-__device__ __forceinline__ void scan_fast(const DevScene& S, const FastScene& F, const TraceQueues& Q,
+template <bool COUNT, class QT = TraceQueues>
+__device__ __forceinline__ void scan_fast(const DevScene& S, const FastScene& F, const QT& Q,
                                           const int* hard, const int* hard_n, int hcap, int bid, int nb, uint32_t* lds,
                                           FastCounters& ctr) {
   const int lane = __lane_id();
   int* stk_node = reinterpret_cast<int*>(lds) + lane;
   float* stk_tmin = reinterpret_cast<float*>(lds) + F.depth * 64 + lane;
-  const QueueIndex QI(Q);
+  const typename queue_index<QT>::type QI(Q);
   const int ns = (F.diag & (32 | 64)) ? 0 : hard_n[1];
   for (int i = bid; i < ns; i += nb) {
     const int e = hard[hcap - 1 - i];

@@ -38,6 +38,7 @@
 #include "winmad_rt.h"
 #include "wr_args.h"
 #include "wr_flatten.h"
+#include "wr_queue_slab.h"
 #include "wr_scene.h"
 #include "wr_traverse.h"
 #include "wr_fast.h"
@@ -125,6 +126,7 @@ constexpr int kShadeBlock = 256;
 #define WR_GROUP 2
 #endif
 constexpr int kGroup = WR_GROUP;
+static_assert(kGroup <= wr::kSlabMaxMembers, "a pipeline's ray slab holds every buffer set of the group");
 
 enum SqKind { SQ_SPLAT = 0, SQ_CONN = 1, SQ_NEE = 2, SQ_DIB = 3 };
 enum DiFlag { DI_NEE = 1, DI_BSDF = 2, DI_EARLY = 4 };
@@ -318,10 +320,15 @@ __device__ __forceinline__ void fast_counts(DevCounters* ctr, const FastCounters
 // cells prove (the resolve's first test) and lists the rest for k_fast_resolve
 // The workgroup is 1 to kMaxSearchWG waves (the launch's choice, wr_fast.h
 // search_wg_bytes); the register budget is amdgpu_waves_per_eu's as before.
-template <bool COUNT, int W, bool SPH, bool RL = false>
+// SLAB: the launch's queues are segments of one ray slab (SlabQueues) -- the
+// search, the resolve and the hard kernels then address a ray by its slab
+// entry alone
+template <bool SLAB>
+using QueuesOf = std::conditional_t<SLAB, SlabQueues, TraceQueues>;
+template <bool COUNT, int W, bool SPH, bool RL = false, bool SLAB = false>
 __global__ void __launch_bounds__(kTraceBlock * kMaxSearchWG)
 __attribute__((amdgpu_waves_per_eu(W == 4 ? WR_FAST4_WAVES : WR_FAST_WAVES, 8))) WR_NO_PK_FP32
-k_trace_fast(DevScene S, FastScene F, TraceQueues Q, DevCounters* ctr, int* fetch, float* t2buf, int2* pairs,
+k_trace_fast(DevScene S, FastScene F, QueuesOf<SLAB> Q, DevCounters* ctr, int* fetch, float* t2buf, int2* pairs,
              int2* spill, int* rlist, int* rlist_n) {
   extern __shared__ uint32_t smem[];
   FastCounters fc{};
@@ -330,18 +337,21 @@ k_trace_fast(DevScene S, FastScene F, TraceQueues Q, DevCounters* ctr, int* fetc
   if (COUNT) fast_counts<COUNT>(ctr, fc);
 }
 // the search kernel for a tree width (instantiated for 2 and 4; 8 when the
-// library is built with WR_BVH_WIDE=8)
-using TraceFastKernel = void (*)(DevScene, FastScene, TraceQueues, DevCounters*, int*, float*, int2*, int2*, int*,
-                                 int*);
-template <bool COUNT>
-TraceFastKernel trace_fast_kernel(int wide, bool sph = false, bool rl = false) {
+// library is built with WR_BVH_WIDE=8, in the general form only)
+template <bool SLAB>
+using TraceFastKernelOf = void (*)(DevScene, FastScene, QueuesOf<SLAB>, DevCounters*, int*, float*, int2*, int2*,
+                                   int*, int*);
+using TraceFastKernel = TraceFastKernelOf<false>;
+template <bool COUNT, bool SLAB = false>
+TraceFastKernelOf<SLAB> trace_fast_kernel(int wide, bool sph = false, bool rl = false) {
 #if WR_BVH_WIDE == 8
-  if (wide == 8) return k_trace_fast<COUNT, 8, false>;  // (triangle scenes: the 8-wide tree is a build option)
+  if constexpr (!SLAB)
+    if (wide == 8) return k_trace_fast<COUNT, 8, false>;  // (triangle scenes: the 8-wide tree is a build option)
 #endif
-  if (sph) return wide == 4 ? k_trace_fast<COUNT, 4, true> : k_trace_fast<COUNT, 2, true>;
+  if (sph) return wide == 4 ? k_trace_fast<COUNT, 4, true, false, SLAB> : k_trace_fast<COUNT, 2, true, false, SLAB>;
   // (the resolve list: triangle trees)
-  if (rl) return wide == 4 ? k_trace_fast<COUNT, 4, false, true> : k_trace_fast<COUNT, 2, false, true>;
-  return wide == 4 ? k_trace_fast<COUNT, 4, false> : k_trace_fast<COUNT, 2, false>;
+  if (rl) return wide == 4 ? k_trace_fast<COUNT, 4, false, true, SLAB> : k_trace_fast<COUNT, 2, false, true, SLAB>;
+  return wide == 4 ? k_trace_fast<COUNT, 4, false, false, SLAB> : k_trace_fast<COUNT, 2, false, false, SLAB>;
 }
 #ifndef WR_RESOLVE_WAVES
 #define WR_RESOLVE_WAVES 0  // > 0: the resolve's register budget as waves per SIMD (0: the compiler's choice, 101 VGPRs)
@@ -351,9 +361,9 @@ TraceFastKernel trace_fast_kernel(int wide, bool sph = false, bool rl = false) {
 #else
 #define WR_RESOLVE_OCC
 #endif
-template <bool COUNT>
+template <bool COUNT, bool SLAB = false>
 __global__ void __launch_bounds__(kTraceBlock) WR_NO_PK_FP32 WR_RESOLVE_OCC
-k_fast_resolve(DevScene S, FastScene F, TraceQueues Q, DevCounters* ctr, const float* t2buf, int* hard, int* hard_n,
+k_fast_resolve(DevScene S, FastScene F, QueuesOf<SLAB> Q, DevCounters* ctr, const float* t2buf, int* hard, int* hard_n,
                int hcap, const int* rlist, const int* rlist_n) {
   FastCounters fc{};
   resolve_fast<COUNT>(S, F, Q, t2buf, hard, hard_n, hcap, fc, rlist, rlist_n);
@@ -378,9 +388,9 @@ k_fast_resolve(DevScene S, FastScene F, TraceQueues Q, DevCounters* ctr, const f
 // as its own tie, and the candidates' replays are shared by its lanes -- and
 // more (full launches, where other pipelines hide the latency) one per lane
 // on the first lane_blocks blocks.
-template <bool COUNT, bool WAVE>
+template <bool COUNT, bool WAVE, bool SLAB = false>
 __global__ void __launch_bounds__(kTraceBlock) WR_NO_PK_FP32 WR_HARD_OCC
-k_fast_hard(DevScene S, FastScene F, TraceQueues Q, DevCounters* ctr, const int* hard, const int* hard_n, int hcap,
+k_fast_hard(DevScene S, FastScene F, QueuesOf<SLAB> Q, DevCounters* ctr, const int* hard, const int* hard_n, int hcap,
             int hard_blocks, int lane_blocks, int wave_max, int pair_blocks) {
   extern __shared__ uint32_t smem[];
   FastCounters fc{};
@@ -690,6 +700,16 @@ struct Upload {
 #define WR_MAX_PIPES 16
 #endif
 constexpr int kMaxPipes = WR_MAX_PIPES;
+// One parity's ray slab of a BDPT pipeline (wr_queue_slab.h): the o / d / t /
+// prim arrays of every buffer set's shadow / aux and extension queues are
+// segments of these (o, d: 3 planes of `stride` entries).  o null: no slab.
+struct RaySlab {
+  float* o = nullptr;
+  float* d = nullptr;
+  float* t = nullptr;
+  int* prim = nullptr;
+  int stride = 0;
+};
 // Each pipeline advances a group of up to kGroup iterations / samples in
 // lockstep: every traversal launch takes the queues of all of them, so the
 // launch tail (its slowest ray) is paid once per group.
@@ -704,6 +724,8 @@ struct Pipe {
   int work_sets = 0;    // buffer sets laid out
   float work_pool = -1.f;  // the BDPT pool scale they were laid out with (bdpt_pool_scale)
   BdptBuf bb[kGroup]{};
+  RaySlab slab[2];            // BDPT layouts: the ray slab of each parity (bb[m].sq[k], bb[m].q_*[k])
+  wr::QueueSlabLayout slab_l;  // ... and its carving (ext segment of set m: cap_ext entries)
   PtBuf pb[kGroup]{};
   VcmBuf vb[kGroup]{};
   DevBuf<float> t2buf;  // WR_TRACE_BVH: 5 floats per ray of a launch: per-ray t2 of the BVH search, lists (TraceSlot)
@@ -808,6 +830,7 @@ struct wr_context {
   bool verify = false;      // WR_BVH_VERIFY=1: every BVH answer checked against the KD walk
   // BDPT light and camera passes overlapped (wr_bdpt.h; env WR_BDPT_OVERLAP=0: sequential)
   bool bdpt_overlap = true;
+  bool queue_slab = true;  // BDPT launches take the slab form of the traversal kernels (env WR_QUEUE_SLAB=0: the general form)
   DevBuf<float> api_t2;    // t2 scratch of the API path (5 floats per ray, as Pipe::t2buf)
   DevBuf<int2> api_spill;  // the API path's search stack spill area
   // ---- several GPUs (wr_create_multi): this context drives devices[0], `subs`
@@ -1045,7 +1068,32 @@ bool bdpt_lds_tables(int nmats, int nlights) {
   return WR_LDS_TABLES != 0 && nmats <= kLdsMats && nlights <= kLdsLights;
 }
 
-void layout_bdpt(Arena& a, BdptBuf& B, int P, bool overlapped, bool vcm = false) {
+// shadow / aux and extension queue capacities of a BDPT buffer set of P paths
+// (layout_bdpt; the extension queue of the overlapped layout holds both passes' rays)
+int bdpt_cap_sq(int P, bool overlapped) {
+  const bool pools = overlapped && bdpt_pool_scale() > 0.f;
+  return pools ? pool_cap(P, kSqPerPath, kVMax + 2, (kVMax + 2) * 64) : P * (kVMax + 2);
+}
+int bdpt_cap_ext(int P, bool overlapped) { return overlapped ? 2 * P : P; }
+// the ray slabs of `sets` BDPT buffer sets (both parities); stride 0: the sizes are out of range
+wr::QueueSlabLayout layout_slab(Arena& a, RaySlab (&slab)[2], int P, bool overlapped, int sets) {
+  const wr::QueueSlabLayout L = wr::queue_slab_layout(sets, bdpt_cap_sq(P, overlapped), bdpt_cap_ext(P, overlapped));
+  const size_t n = L.stride;
+  for (RaySlab& s : slab) {
+    s.o = a.take<float>(3 * n);
+    s.d = a.take<float>(3 * n);
+    s.t = a.take<float>(n);
+    s.prim = a.take<int>(n);
+    s.stride = L.stride;
+  }
+  return L;
+}
+
+// slab, L, set: the ray arrays the traversal reads and writes (sq o / d / t /
+// prim, q_o / q_d / q_t / q_prim) are segments of the pipeline's ray slabs and
+// B.qs is the slabs' plane stride (BDPT); null: arrays of the set's own (VertexCM)
+void layout_bdpt(Arena& a, BdptBuf& B, int P, bool overlapped, bool vcm = false, const RaySlab* slab = nullptr,
+                 const wr::QueueSlabLayout* L = nullptr, int set = 0) {
   B.P = P;
   // shadow / aux rays queued by one step, per path: sequential schedule, a
   // camera vertex's <= kVMax connections + NEE + DI-BSDF (the light splats of
@@ -1055,7 +1103,7 @@ void layout_bdpt(Arena& a, BdptBuf& B, int P, bool overlapped, bool vcm = false)
   // sized by use (kSqPerPath), the vertex stores pools (kVPoolPerPath,
   // kCPoolPerPath) -- 1.0 KB per path instead of 3.0 KB
   const bool pools = overlapped && bdpt_pool_scale() > 0.f;
-  B.cap_sq = pools ? pool_cap(P, kSqPerPath, kVMax + 2, (kVMax + 2) * 64) : P * (kVMax + 2);
+  B.cap_sq = bdpt_cap_sq(P, overlapped);
   B.vcap = pools ? pool_cap(P, kVPoolPerPath, kVMax, kVMax * 64) : kVMax * P;
   B.ccap = pools ? pool_cap(P, kCPoolPerPath, kCvMax, kCvMax * 64) : kCvMax * P;
   const size_t sP = P, sV = size_t(B.vcap), sQ = B.cap_sq;
@@ -1077,27 +1125,43 @@ void layout_bdpt(Arena& a, BdptBuf& B, int P, bool overlapped, bool vcm = false)
   B.vidx = pools ? a.take<int>(size_t(kVMax) * P) : nullptr;
   B.cidx = pools ? a.take<int>(size_t(kCvMax) * P) : nullptr;
   // overlapped: an extension queue holds both passes' rays (light, then camera)
-  B.qs = overlapped ? 2 * P : P;
-  const size_t sE = B.qs;
+  const size_t sE = bdpt_cap_ext(P, overlapped);
+  B.qs = slab ? L->stride : static_cast<int>(sE);
 
   for (int q = 0; q < 2; ++q) {
-    B.q_o[q] = a.take<float>(3 * sE);
-    B.q_d[q] = a.take<float>(3 * sE);
-    B.q_t[q] = a.take<float>(sE);
+    if (slab) {
+      const size_t e0 = L->ext_base[set];
+      B.q_o[q] = slab[q].o + e0;
+      B.q_d[q] = slab[q].d + e0;
+      B.q_t[q] = slab[q].t + e0;
+      B.q_prim[q] = slab[q].prim + e0;
+    } else {
+      B.q_o[q] = a.take<float>(3 * sE);
+      B.q_d[q] = a.take<float>(3 * sE);
+      B.q_t[q] = a.take<float>(sE);
+      B.q_prim[q] = a.take<int>(sE);
+    }
     B.q_path[q] = a.take<int>(sE);
-    B.q_prim[q] = a.take<int>(sE);
   }
   for (int k = 0; k < 2; ++k) {
     BdptBuf::Sq& q = B.sq[k];
-    q.o = a.take<float>(3 * sQ);
-    q.d = a.take<float>(3 * sQ);
+    if (slab) {
+      const size_t s0 = L->sq_base[set];
+      q.o = slab[k].o + s0;
+      q.d = slab[k].d + s0;
+      q.t = slab[k].t + s0;
+      q.prim = slab[k].prim + s0;
+    } else {
+      q.o = a.take<float>(3 * sQ);
+      q.d = a.take<float>(3 * sQ);
+      q.t = a.take<float>(sQ);
+      q.prim = a.take<int>(sQ);
+    }
     q.tgt = a.take<float>(3 * sQ);
     q.val = a.take<float>(3 * sQ);
-    q.t = a.take<float>(sQ);
     q.cut = a.take<float>(sQ);
     q.meta = a.take<int>(sQ);
     q.pix = a.take<int>(sQ);
-    q.prim = a.take<int>(sQ);
     B.di[k].r = a.take<float>(DR_WORDS * sP);
   }
 }
@@ -1169,17 +1233,36 @@ void layout_vcm(Arena& a, VcmBuf& V, int P) {
   V.scan_tmp = a.take<char>(V.scan_bytes);
 }
 
-// one buffer set of `kind` (into dst's set g, or only measured)
-void layout_set(Arena& a, Pipe* dst, int g, int kind, int P) {
-  BdptBuf b;
-  PtBuf t;
-  VcmBuf v;
-  if (kind == 2) {
-    layout_pt(a, dst ? dst->pb[g] : t, P);
-    return;
+// `sets` buffer sets of `kind` (into dst's, or only measured).  BDPT: the ray
+// slabs first, then each set's own arrays.  False: sizes out of the slab's range
+bool layout_sets(Arena& a, Pipe* dst, int sets, int kind, int P) {
+  RaySlab slab[2];
+  wr::QueueSlabLayout L;
+  if (kind == 1) {
+    L = layout_slab(a, slab, P, true, sets);
+    if (L.stride == 0) return false;
+    if (dst) {
+      dst->slab[0] = slab[0];
+      dst->slab[1] = slab[1];
+      dst->slab_l = L;
+    }
+  } else if (dst) {
+    dst->slab[0] = dst->slab[1] = RaySlab{};
+    dst->slab_l = wr::QueueSlabLayout{};
   }
-  layout_bdpt(a, dst ? dst->bb[g] : b, P, kind == 1, kind == 3);
-  if (kind == 3) layout_vcm(a, dst ? dst->vb[g] : v, P);
+  for (int g = 0; g < sets; ++g) {
+    BdptBuf b;
+    PtBuf t;
+    VcmBuf v;
+    if (kind == 2) {
+      layout_pt(a, dst ? dst->pb[g] : t, P);
+      continue;
+    }
+    if (kind == 1) layout_bdpt(a, dst ? dst->bb[g] : b, P, true, false, slab, &L, g);
+    else layout_bdpt(a, dst ? dst->bb[g] : b, P, false, kind == 3);
+    if (kind == 3) layout_vcm(a, dst ? dst->vb[g] : v, P);
+  }
+  return true;
 }
 
 int ensure_work(Pipe& p, int kind, int P, int sets) {
@@ -1187,12 +1270,12 @@ int ensure_work(Pipe& p, int kind, int P, int sets) {
   const bool same = p.work_kind == kind && p.work_pool == bdpt_pool_scale();
   if (same && p.work_key == static_cast<size_t>(P) && p.work_sets >= sets) return WR_OK;
   p.work_kind = 0;
-  auto lay = [&](Arena& a, Pipe* dst) {
-    for (int g = 0; g < sets; ++g) layout_set(a, dst, g, kind, P);
-  };
-  int rc = p.work.reserve(measure([&](Arena& a) { lay(a, nullptr); }));
+  bool ok = true;
+  const size_t need = measure([&](Arena& a) { ok = layout_sets(a, nullptr, sets, kind, P); });
+  if (!ok) return WR_E_ARG;  // (a film too large for the ray slab's int indices)
+  int rc = p.work.reserve(need);
   if (rc) return rc;
-  lay(p.work, &p);
+  layout_sets(p.work, &p, sets, kind, P);
   p.work_kind = kind;
   p.work_key = P;
   p.work_sets = sets;
@@ -1206,9 +1289,7 @@ int ensure_work(Pipe& p, int kind, int P, int sets) {
 // failing.  Every render lays out full groups on all pipelines that fit, so a
 // short render (a warm-up) leaves the buffers of a long one in place.
 int pipelines_that_fit(wr_context* c, int kind, int P, int sets, int want) {
-  const size_t per = measure([&](Arena& a) {
-    for (int g = 0; g < sets; ++g) layout_set(a, nullptr, g, kind, P);
-  });
+  const size_t per = measure([&](Arena& a) { (void)layout_sets(a, nullptr, sets, kind, P); });
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return want;
   size_t held = 0;
@@ -1270,15 +1351,47 @@ int host_count(const RayQueue& q) {
 struct QueueList {
   TraceQueues Q{};
   int max_rays = 0;
-  void add(const RayQueue& q, int cap) {
+  // lim: the rays the queue holds at most (a slab segment's entries); < 0: its plane stride q.cap
+  void add(const RayQueue& q, int cap, int lim = -1) {
     if (Q.n >= kMaxQueues) {  // a schedule asking for more queues than a launch takes: a build error
       std::fprintf(stderr, "winmad_rt: more than %d queues in one traversal launch\n", kMaxQueues);
       std::abort();
     }
+    Q.lim[Q.n] = lim < 0 ? q.cap : lim;
     Q.q[Q.n++] = q;
     max_rays += cap;
   }
 };
+// The slab form of a launch's queues, if they are one slab: every queue's
+// arrays lie at one entry offset (shift) from the slab's, the plane stride is
+// the slab's entries for all of them, each segment [shift, shift + lim) is
+// inside a plane, no two segments overlap, and no queue has per-ray
+// [tmin, tmax].  False otherwise: the launch keeps the general form.
+bool slab_form(const TraceQueues& Q, const RaySlab& sl, SlabQueues& out) {
+  if (!sl.o || Q.n < 1) return false;
+  SlabQueues s{};
+  s.o3 = sl.o;
+  s.d3 = sl.d;
+  s.out_t = sl.t;
+  s.out_prim = sl.prim;
+  s.stride = sl.stride;
+  s.n = Q.n;
+  for (int i = 0; i < Q.n; ++i) {
+    const RayQueue& q = Q.q[i];
+    const ptrdiff_t sh = q.o3 - sl.o;
+    if (q.d3 - sl.d != sh || q.out_t - sl.t != sh || q.out_prim - sl.prim != sh) return false;
+    if (q.cap != sl.stride || q.tmin || q.tmax) return false;
+    if (sh < 0 || Q.lim[i] < 0 || sh + Q.lim[i] > sl.stride) return false;
+    for (int j = 0; j < i; ++j)
+      if (sh < s.shift[j] + s.lim[j] && s.shift[j] < sh + Q.lim[i]) return false;
+    s.shift[i] = static_cast<int>(sh);
+    s.lim[i] = Q.lim[i];
+    s.count[i] = q.count;
+    s.count2[i] = q.count2;
+  }
+  out = s;
+  return true;
+}
 
 using TraceKernel = void (*)(DevScene, TraceQueues, DevCounters*, int*);
 // cut: the launch's shadow rays may stop once occlusion is settled (occl_cut).
@@ -1380,7 +1493,8 @@ static void log_rounds(const unsigned long long r[4]) {
 }
 
 int trace_launch(wr_context* c, hipStream_t stream, DevCounters* ctr, const TraceSlot& ts, Timer& tm, bool count,
-                 const TraceQueues& Q_, int max_rays, int mode = TRACE_PLAIN, bool hard_wave = false) {
+                 const TraceQueues& Q_, int max_rays, int mode = TRACE_PLAIN, bool hard_wave = false,
+                 const RaySlab* slab = nullptr) {
   int* fetch = ts.fetch;
   TraceQueues Q = Q_;
   if (c->no_cut)  // measurement knob: the same launches without the dead-work elision
@@ -1413,15 +1527,28 @@ int trace_launch(wr_context* c, hipStream_t stream, DevCounters* ctr, const Trac
       (void)hipEventCreate(&fb);
       (void)hipEventRecord(f0, stream);
     }
-    auto kf = count ? trace_fast_kernel<true>(F.wide, F.sph, rl) : trace_fast_kernel<false>(F.wide, F.sph, rl);
-    hipLaunchKernelGGL(kf, dim3(fgrid), dim3(kTraceBlock * wg), rlds, stream, c->ds, F, Q, ctr, fetch, ts.t2, pairs,
-                       ts.spill, rlist, rlist_n);
-    if (c->trace_log) (void)hipEventRecord(fa, stream);
+    // the slab form, when the caller's queues are one ray slab (BDPT; the
+    // pipelines' hard kernel only: one tie per wave is the API paths').
+    // WR_QUEUE_SLAB=0 keeps the general form, and so does the 8-wide build option
+    SlabQueues SQ{};
+    const bool slabbed = c->queue_slab && slab && !hard_wave && F.wide != 8 && slab_form(Q, *slab, SQ);
+    const dim3 rgrid(std::max(1, std::min(c->resolve_blocks > 0 ? c->resolve_blocks : c->fast_blocks, blocks)));
     int* hard = reinterpret_cast<int*>(ts.t2 + ts.t2_cap);
-    hipLaunchKernelGGL(count ? k_fast_resolve<true> : k_fast_resolve<false>,
-                       dim3(std::max(1, std::min(c->resolve_blocks > 0 ? c->resolve_blocks : c->fast_blocks, blocks))),
-                       dim3(kTraceBlock), 0, stream, c->ds, F,
-                       Q, ctr, ts.t2, hard, ts.hard_n, static_cast<int>(ts.t2_cap), rlist, rlist_n);
+    if (slabbed) {
+      auto kf = count ? trace_fast_kernel<true, true>(F.wide, F.sph, rl) : trace_fast_kernel<false, true>(F.wide, F.sph, rl);
+      hipLaunchKernelGGL(kf, dim3(fgrid), dim3(kTraceBlock * wg), rlds, stream, c->ds, F, SQ, ctr, fetch, ts.t2, pairs,
+                         ts.spill, rlist, rlist_n);
+      if (c->trace_log) (void)hipEventRecord(fa, stream);
+      auto kr = count ? k_fast_resolve<true, true> : k_fast_resolve<false, true>;
+      hipLaunchKernelGGL(kr, rgrid, dim3(kTraceBlock), 0, stream, c->ds, F, SQ, ctr, ts.t2, hard, ts.hard_n, static_cast<int>(ts.t2_cap), rlist, rlist_n);
+    } else {
+      auto kf = count ? trace_fast_kernel<true>(F.wide, F.sph, rl) : trace_fast_kernel<false>(F.wide, F.sph, rl);
+      hipLaunchKernelGGL(kf, dim3(fgrid), dim3(kTraceBlock * wg), rlds, stream, c->ds, F, Q, ctr, fetch, ts.t2, pairs,
+                         ts.spill, rlist, rlist_n);
+      if (c->trace_log) (void)hipEventRecord(fa, stream);
+      hipLaunchKernelGGL(count ? k_fast_resolve<true> : k_fast_resolve<false>, rgrid, dim3(kTraceBlock), 0, stream, c->ds,
+                         F, Q, ctr, ts.t2, hard, ts.hard_n, static_cast<int>(ts.t2_cap), rlist, rlist_n);
+    }
     if (c->trace_log) (void)hipEventRecord(fb, stream);
     // the hard rays are a few in 10^4: a small grid drains any count (one
     // ray per wave for the API calls: up to 2048 at once, 8 waves per CU)
@@ -1434,9 +1561,14 @@ int trace_launch(wr_context* c, hipStream_t stream, DevCounters* ctr, const Trac
                         : (count ? k_fast_hard<true, false> : k_fast_hard<false, false>);
     // the pair list (near-ties the search's pair record settles, one per lane)
     const int pgrid = (F.diag || F.pair < 2) ? 0 : lgrid;
-    hipLaunchKernelGGL(hk, dim3(hgrid + pgrid + sgrid),
-                       dim3(kTraceBlock), lds, stream, c->ds, F, Q, ctr, hard, ts.hard_n,
-                       static_cast<int>(ts.t2_cap), hgrid, lgrid, std::min(hgrid, c->tie_wave_max), pgrid);
+    auto hks = count ? k_fast_hard<true, false, true> : k_fast_hard<false, false, true>;
+    if (slabbed)
+      hipLaunchKernelGGL(hks, dim3(hgrid + pgrid + sgrid), dim3(kTraceBlock), lds, stream, c->ds, F, SQ, ctr, hard, ts.hard_n,
+                         static_cast<int>(ts.t2_cap), hgrid, lgrid, std::min(hgrid, c->tie_wave_max), pgrid);
+    else
+      hipLaunchKernelGGL(hk, dim3(hgrid + pgrid + sgrid),
+                         dim3(kTraceBlock), lds, stream, c->ds, F, Q, ctr, hard, ts.hard_n,
+                         static_cast<int>(ts.t2_cap), hgrid, lgrid, std::min(hgrid, c->tie_wave_max), pgrid);
     if (c->verify)
       hipLaunchKernelGGL(k_fast_verify, dim3(std::max(1, std::min(c->fast_blocks, blocks))), dim3(kTraceBlock), lds,
                          stream, c->ds, F, Q, ctr);
@@ -1919,6 +2051,7 @@ static void read_knobs(wr_context& c) {
   if (const char* e = std::getenv("WR_SCAN_WAVES")) c.scan_waves = std::max(1, std::atoi(e));
   if (const char* e = std::getenv("WR_ISSUE_THREADS")) c.issue_threads = std::max(1, std::min(kMaxPipes, std::atoi(e)));
   if (const char* e = std::getenv("WR_BDPT_OVERLAP")) c.bdpt_overlap = std::atoi(e) != 0;
+  if (const char* e = std::getenv("WR_QUEUE_SLAB")) c.queue_slab = std::atoi(e) != 0;
   // k_fast_resolve's grid, given in blocks per CU
   if (const char* e = std::getenv("WR_RESOLVE_GRID")) c.resolve_blocks = std::max(0, std::atoi(e)) * c.cus;
   if (const char* e = std::getenv("WR_RESOLVE_LIST")) c.resolve_list = std::atoi(e) != 0;
@@ -2121,6 +2254,11 @@ static int upload_bvh(wr_context& c, const wr::Scene& s, const wr::SceneFlat& f,
         for (int w : {wide, c.fs4_ok ? 4 : wide}) {
           const TraceFastKernel kf = cnt ? trace_fast_kernel<true>(w, fs.sph, rl) : trace_fast_kernel<false>(w, fs.sph, rl);
           HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     static_cast<int>(wg_bytes(wg))));
+          if (w == 8) continue;  // (no slab form of the 8-wide build option)
+          const TraceFastKernelOf<true> ks =
+              cnt ? trace_fast_kernel<true, true>(w, fs.sph, rl) : trace_fast_kernel<false, true>(w, fs.sph, rl);
+          HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      static_cast<int>(wg_bytes(wg))));
         }
   const size_t wgb = search_wg_bytes(fs.sdepth, wide, c.resolve_list, fs.ntop, wg);
@@ -2660,15 +2798,17 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     for (int m = 0; m < gn; ++m) {
       const BdptBuf& B = pp.bb[m];
       const BdptBuf::Sq& Q = B.sq[slot & 1];
-      ql.add(rq(Q.o, Q.d, B.cap_sq, &pp.sc[m].sq[slot], Q.t, Q.prim, Q.cut),
-             std::min(A[m].n * (kVMax + 2), B.cap_sq));
+      // (segments of the pipeline's ray slab: plane stride B.qs, clamped to the segment)
+      ql.add(rq(Q.o, Q.d, B.qs, &pp.sc[m].sq[slot], Q.t, Q.prim, Q.cut), std::min(A[m].n * (kVMax + 2), B.cap_sq),
+             B.cap_sq);
       if (light || more) {
         RayQueue e = rq(B.q_o[b & 1], B.q_d[b & 1], B.qs, &pp.sc[m].ext[b], B.q_t[b & 1], B.q_prim[b & 1]);
         e.count2 = &pp.sc[m].ext[slot];  // the camera pass's rays, behind the light pass's
-        ql.add(e, 2 * A[m].n);
+        ql.add(e, 2 * A[m].n, pp.slab_l.cap_ext);
       }
     }
-    trace_launch(c, sm, pp.ctr, tslot(pp, slot), tm, count, ql.Q, ql.max_rays, WR_BDPT_TRACE_MODE);
+    trace_launch(c, sm, pp.ctr, tslot(pp, slot), tm, count, ql.Q, ql.max_rays, WR_BDPT_TRACE_MODE, false,
+                 &pp.slab[slot & 1]);
     if (light) hipLaunchKernelGGL(k_lshade, dim3(g, gn), dim3(kShadeBlock), 0, sm, G.GA, b);
     const int nres = shade_grid(c, std::min(G.nmax * (kVMax + 2), pp.bb[0].cap_sq));
     hipLaunchKernelGGL(k_cstep, dim3(nres + (more ? g : 0), gn), dim3(kShadeBlock), 0, sm, G.GA, slot, nres,
@@ -2689,13 +2829,14 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     const BdptArgs* A = G.GA.a;
     auto sq = [&](int m, int slot) {
       const BdptBuf::Sq& Q = pp.bb[m].sq[slot & 1];
-      return rq(Q.o, Q.d, pp.bb[m].cap_sq, &pp.sc[m].sq[slot], Q.t, Q.prim, Q.cut);
+      return rq(Q.o, Q.d, pp.bb[m].qs, &pp.sc[m].sq[slot], Q.t, Q.prim, Q.cut);  // (ray slab: plane stride qs)
     };
     auto ext = [&](int m, int slot) {  // extension rays of step `slot`
       const BdptBuf& B = pp.bb[m];
       const int q = slot & 1;
       return rq(B.q_o[q], B.q_d[q], B.qs, &pp.sc[m].ext[slot], B.q_t[q], B.q_prim[q]);
     };
+    const int ext_lim = pp.slab_l.cap_ext;
     const int sq_max = std::min(G.nmax * (kVMax + 2), pp.bb[0].cap_sq);
     const int g = shade_grid(c, G.nmax);
     if (step == 0) {
@@ -2706,8 +2847,9 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
     } else if (step <= lb_n) {
       const int b = step - 1;
       QueueList ql;
-      for (int m = 0; m < gn; ++m) ql.add(ext(m, b), A[m].n);
-      trace_launch(c, sm, pp.ctr, tslot(pp, b), tm, count, ql.Q, ql.max_rays, WR_BDPT_TRACE_MODE);
+      for (int m = 0; m < gn; ++m) ql.add(ext(m, b), A[m].n, ext_lim);
+      trace_launch(c, sm, pp.ctr, tslot(pp, b), tm, count, ql.Q, ql.max_rays, WR_BDPT_TRACE_MODE, false,
+                   &pp.slab[b & 1]);
       hipLaunchKernelGGL(k_lshade, dim3(g, gn), dim3(kShadeBlock), 0, sm, G.GA, b);
       tm.mark(WR_K_SHADE);
     } else if (step == lb_n + 1) {
@@ -2721,10 +2863,12 @@ static int render_bdpt_one(wr_context* c, const wr_bdpt_params* prm, int64_t f_l
       const int slot = kCamSlot + b;
       const bool more = b < maxlen;  // extension rays of bounce b exist
       QueueList ql;
-      for (int m = 0; m < gn; ++m) ql.add(sq(m, slot), std::min(A[m].n * (kVMax + 2), pp.bb[m].cap_sq));
+      for (int m = 0; m < gn; ++m)
+        ql.add(sq(m, slot), std::min(A[m].n * (kVMax + 2), pp.bb[m].cap_sq), pp.bb[m].cap_sq);
       if (more)
-        for (int m = 0; m < gn; ++m) ql.add(ext(m, slot), A[m].n);
-      trace_launch(c, sm, pp.ctr, tslot(pp, slot), tm, count, ql.Q, ql.max_rays, WR_BDPT_TRACE_MODE);
+        for (int m = 0; m < gn; ++m) ql.add(ext(m, slot), A[m].n, ext_lim);
+      trace_launch(c, sm, pp.ctr, tslot(pp, slot), tm, count, ql.Q, ql.max_rays, WR_BDPT_TRACE_MODE, false,
+                   &pp.slab[slot & 1]);
       // resolve this step's shadow / aux rays and shade its vertices in one launch
       const int nres = shade_grid(c, sq_max);
       hipLaunchKernelGGL(k_cstep, dim3(nres + (more ? g : 0), gn), dim3(kShadeBlock), 0, sm, G.GA, slot, nres,

@@ -210,6 +210,29 @@ constexpr int kMaxQueues = WR_MAX_QUEUES;
 struct TraceQueues {
   RayQueue q[kMaxQueues];
   int n;
+  // the most rays queue i holds, which its count is clamped to.  RayQueue::cap
+  // is the plane stride of o3 / d3; the two differ for a segment of a ray slab
+  // (behind n: the offsets of q and n are the same with and without it)
+  int lim[kMaxQueues];
+};
+
+// The slab form of a launch whose queues are segments of one ray slab
+// (wr_queue_slab.h): one base pointer per field and one plane stride for the
+// whole launch, and per queue only where its segment starts.  The ray of
+// launch index idx in queue q, r is entry e = r + shift[q] of every array:
+// o3[e], o3[stride + e], o3[2 * stride + e].  No per-ray [tmin, tmax]: a
+// launch that has them keeps the general form.
+struct SlabQueues {
+  const float* o3;
+  const float* d3;
+  float* out_t;
+  int* out_prim;
+  int stride;
+  int n;
+  int shift[kMaxQueues];
+  int lim[kMaxQueues];  // shift[i] + lim[i] <= stride (the host checks)
+  const int* count[kMaxQueues];
+  const int* count2[kMaxQueues];
 };
 
 // Per-wave LDS scratch of the traversal (one wave per workgroup, 64 lanes):
@@ -396,7 +419,7 @@ __device__ __forceinline__ void trace_queue(const DevScene& S, const TraceQueues
 #pragma unroll
     for (int i = 0; i < kMaxQueues; ++i) {
       // (capped: a shadow queue's appends past its capacity were dropped, BdptBuf)
-      if (i < Q.n && Q.q[i].count) acc += min(*Q.q[i].count + (Q.q[i].count2 ? *Q.q[i].count2 : 0), Q.q[i].cap);
+      if (i < Q.n && Q.q[i].count) acc += min(*Q.q[i].count + (Q.q[i].count2 ? *Q.q[i].count2 : 0), Q.lim[i]);
       qend[i] = acc;
     }
   }

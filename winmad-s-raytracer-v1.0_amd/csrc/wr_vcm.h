@@ -699,7 +699,7 @@ __global__ void __launch_bounds__(kShadeBlock) WR_SHADE_OCC k_vcm_camera_step(Vc
                                                                              int nsh) {
   const VcmArgs& X = G_.a[blockIdx.y];
   const int bx = static_cast<int>(blockIdx.x);
-  if (bx < nres) sq_resolve_body(X.a, slot, bx, nres);
+  if (bx < nres) sq_resolve_body<true>(X.a, slot, bx, nres);
   else if (bx < nres + nsh) vcm_camera_shade_body(X, slot, bx - nres, nsh);
   else vcm_merge_body(X, slot - 1, bx - nres - nsh, gridDim.x - nres - nsh);
 }
