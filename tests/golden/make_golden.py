@@ -10,6 +10,7 @@ box uses the committed fixtures.
     python tests/golden/make_golden.py          (everything)
     python tests/golden/make_golden.py image    (the 8-bit image fixtures only)
     python tests/golden/make_golden.py zoo      (the material-zoo fixtures only)
+    python tests/golden/make_golden.py geozoo   (the geometry-zoo ray fixtures only; golden_geozoo.json)
 """
 import gzip
 import hashlib
@@ -24,6 +25,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(REPO, "winmad-s-raytracer-v1.0_amd"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
 from winmad_rt import scenes  # noqa: E402
 
 REFDRV = os.path.join(REPO, "oracle", "_ref", "refdrv")
@@ -290,6 +292,105 @@ def zoo_fixtures(tmp):
     write_gz("kat_zoo_edges.txt.gz", refdrv("katin", sp, pp, cp, cwd=tmp))
 
 
+# ---------------------------------------------------------------- geometry zoo
+# Ray corpora on the scenes of tests/_geometry_zoo.py and the reference's answers.
+GEOZOO_N = 1024       # rays per corpus half (a `far` family has two halves)
+GEOZOO_BOX = 3.0      # every family's own geometry lies within +-2.5 of the origin
+
+
+def _unit_rows(v):
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def geozoo_corpus(name, lo, hi, seed, far):
+    """GEOZOO_N rays (o, d, occlusion target) in four equal quarters: aimed at the
+    family's corners exactly; at points on the segment between two corners (half:
+    an edge of one triangle, half: any two corners); at random points of the
+    scene box [lo, hi]; and along +-an axis from origins on the half-integer
+    lattice.  Origins: a quarter inside the geometry's box, the rest 4 to 12
+    units from the origin -- or, for every other ray of a `far` corpus, 5,000 to
+    20,000 units away, mostly above the floor so that what misses the family
+    meets the floor at t >= 4096.  Targets lie on the ray, before or beyond the
+    point aimed at (half of the hitting rays get their hit point, geozoo_fixtures)."""
+    import _geometry_zoo as gz
+    rng = np.random.default_rng(seed)
+    n, q = GEOZOO_N, GEOZOO_N // 4
+    corners, segs = gz.aim_points(name)
+    is_far = far & (np.arange(n) % 2 == 1)
+    u = _unit_rows(rng.normal(size=(n, 3)))
+    up = rng.random(n) < 0.75
+    u[:, 2] = np.where(is_far & up, np.abs(u[:, 2]) + 1.0, u[:, 2])
+    u = _unit_rows(u)
+    dist = np.where(is_far, rng.uniform(5000.0, 20000.0, n), rng.uniform(4.0, 12.0, n))
+    o = u * dist[:, None]
+    inside = (rng.random(n) < 0.25) & ~is_far
+    o[inside] = rng.uniform(-GEOZOO_BOX, GEOZOO_BOX, (int(inside.sum()), 3))
+    o = o.astype(np.float32)
+    aim = np.zeros((n, 3), np.float32)
+    aim[:q] = corners[rng.integers(0, len(corners), q)]
+    s = segs[rng.integers(0, len(segs), q)]
+    any2 = rng.random(q) < 0.5
+    s[any2, 0] = corners[rng.integers(0, len(corners), int(any2.sum()))]
+    s[any2, 1] = corners[rng.integers(0, len(corners), int(any2.sum()))]
+    w = rng.random((q, 1)).astype(np.float32)
+    aim[q:2 * q] = s[:, 0] + (s[:, 1] - s[:, 0]) * w
+    aim[2 * q:3 * q] = (lo + (hi - lo) * rng.random((q, 3))).astype(np.float32)
+    d = (aim - o).astype(np.float32)
+    # axis-parallel quarter
+    k = np.arange(3 * q, n)
+    axis = rng.integers(0, 3, q)
+    sign = np.where(rng.random(q) < 0.5, 1.0, -1.0)
+    oa = np.round(2.0 * rng.uniform(-GEOZOO_BOX, GEOZOO_BOX, (q, 3))) / 2.0
+    along = np.round(2.0 * dist[k]) / 2.0
+    along = np.where(inside[k], oa[np.arange(q), axis], -sign * along)
+    oa[np.arange(q), axis] = along
+    da = np.zeros((q, 3))
+    da[np.arange(q), axis] = sign
+    o[k], d[k] = oa.astype(np.float32), da.astype(np.float32)
+    aim[k] = (oa + da * np.abs(along)[:, None]).astype(np.float32)
+    out = np.zeros((n, 9), np.float32)
+    out[:, 0:3], out[:, 3:6] = o, d
+    out[:, 6:9] = o + (aim - o) * (2.0 * rng.random((n, 1))).astype(np.float32)
+    return out
+
+
+def geozoo_fixtures(tmp):
+    import _geometry_zoo as gz
+    meta = {}
+    pp = scenes.write(os.path.join(tmp, "geozoo.para"), scenes.params_text(32, 32))
+    for i, name in enumerate(gz.NAMES):
+        sp = gz.scene(name)
+        dump = refdrv("scene", sp, pp, cwd=tmp)
+        lines = dump.splitlines()
+        meta[name] = {
+            "scene_sha256": sha(dump),
+            "nobjs": int(lines[0].split()[1]),
+            "inner": sum(1 for l in lines if l.startswith("I ")),
+            "leaves": sum(1 for l in lines if l.startswith("L ")),
+            "refs": sum(int(l.split()[1]) for l in lines if l.startswith("L ")),
+            "depmax": int(next(l for l in lines if l.startswith("kd ")).split()[1]),
+        }
+        kd = [float.fromhex(t) for t in next(l for l in lines if l.startswith("kd ")).split()[2:]]
+        lo, hi = np.array(kd[:3]), np.array(kd[3:6])
+        halves = [geozoo_corpus(name, lo, hi, 7000 + i, False)]
+        if name in gz.FAR:
+            halves.append(geozoo_corpus(name, lo, hi, 7100 + i, True))
+        corpus = np.concatenate(halves)
+        cp = os.path.join(HERE, f"geozoo_{name}.f32")
+        corpus.tofile(cp)
+        # second pass, as for rays_*.f32: every other hitting ray gets its own hit point as target
+        for k, line in enumerate(refdrv("rays", sp, pp, cp, cwd=tmp).splitlines()):
+            tok = line.split()
+            if tok[0] != "-1" and k % 2 == 0:
+                corpus[k, 6:9] = [float.fromhex(t) for t in tok[2:5]]
+        corpus.tofile(cp)
+        write_gz(f"geozoo_{name}.txt.gz", refdrv("rays", sp, pp, cp, cwd=tmp))
+    with open(os.path.join(HERE, "golden_geozoo.json"), "w") as f:
+        json.dump(meta, f, indent=1)
+        f.write("\n")
+    print(json.dumps(meta, indent=1))
+
+
 class _FirstOfRun(dict):
     """probs of the r3.z run that starts at a record index ((0, 0, 0) for an invalid BSDF)."""
 
@@ -303,6 +404,9 @@ def main():
         return
     if len(sys.argv) > 1 and sys.argv[1] == "zoo":  # the material-zoo fixtures alone
         zoo_fixtures(tempfile.mkdtemp(prefix="wr_golden_"))
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "geozoo":  # the geometry-zoo fixtures alone
+        geozoo_fixtures(tempfile.mkdtemp(prefix="wr_golden_"))
         return
     if not os.path.exists(REFDRV):
         sys.exit("build the reference driver first: make -C oracle ref")
@@ -389,6 +493,7 @@ def main():
         refdrv("vcm", sp, pp, it, seed, os.path.join(HERE, vcm_fixture(name, it, seed, rf)), *extra, cwd=tmp)
     image_fixtures(tmp)
     zoo_fixtures(tmp)
+    geozoo_fixtures(tmp)
     with open(os.path.join(HERE, "golden.json"), "w") as f:
         json.dump(meta, f, indent=1)
     print(json.dumps({k: v for k, v in meta.items() if "block32_mean" not in v}, indent=1))

@@ -797,6 +797,7 @@ void build_fast(const wr::Scene& s, FastHost& out, int wide, bool with4, int top
     }
   }
   for (const auto& p : s.prims) out.spheres += p.type != wr::kTri ? 1 : 0;
+  std::atomic<long long> sliver{-1};  // a triangle Cramer's rule cannot solve for any ray (kSliverSin)
   auto prep = [&](size_t i0, size_t i1) {
     for (size_t i = i0; i < i1; ++i) {
       const wr::Prim& p = s.prims[i];
@@ -834,6 +835,15 @@ void build_fast(const wr::Scene& s, FastHost& out, int wide, bool with4, int top
         const double x = a[0] - c[0], y = a[1] - c[1], z = a[2] - c[2];
         return std::sqrt(x * x + y * y + z * z);
       };
+      {
+        // p0 == p1 or p0 == p2 makes the denominator an exact zero (no hit for
+        // any ray); collinear or nearly collinear vertices leave its rounding noise
+        const double e1[3] = {double(v[1][0]) - v[0][0], double(v[1][1]) - v[0][1], double(v[1][2]) - v[0][2]};
+        const double e2[3] = {double(v[2][0]) - v[0][0], double(v[2][1]) - v[0][1], double(v[2][2]) - v[0][2]};
+        const double nx = e1[1] * e2[2] - e1[2] * e2[1], ny = e1[2] * e2[0] - e1[0] * e2[2], nz = e1[0] * e2[1] - e1[1] * e2[0];
+        const double l1 = len(v[0], v[1]), l2 = len(v[0], v[2]);
+        if (l1 > 0.0 && l2 > 0.0 && std::sqrt(nx * nx + ny * ny + nz * nz) <= kSliverSin * l1 * l2) sliver.store(static_cast<long long>(i));
+      }
       const double m = kBoxGrow * (len(v[0], v[1]) + len(v[0], v[2])) + 1e-6 * (1.0 + std::max({std::fabs(b.lo[0]),
           std::fabs(b.lo[1]), std::fabs(b.lo[2]), std::fabs(b.hi[0]), std::fabs(b.hi[1]), std::fabs(b.hi[2])}));
       for (int k = 0; k < 3; ++k) {
@@ -854,6 +864,10 @@ void build_fast(const wr::Scene& s, FastHost& out, int wide, bool with4, int top
   prep(0, std::min(n, chunk));
   for (auto& f : parts) f.get();
   kd.get();
+  if (sliver.load() >= 0) {
+    out.why = "a triangle with nearly collinear vertices (primitive " + std::to_string(sliver.load()) + ")";
+    return;
+  }
   out.ok = true;
   out.tris.reserve(n);
   out.nodes.reserve(2 * n / kMaxLeaf + 8);

@@ -154,6 +154,13 @@ constexpr int kMaxLeaf = WR_BVH_LEAF;  // triangles per BVH leaf (<= 8)
 constexpr int kMaxBvhDepth = 62;       // deeper builds disable the fast path
 constexpr float kBoxGrow = WR_BVH_BOX_GROW;  // x (|p0 - p1| + |p0 - p2|): 2x the EPS fattening (0.01: C2 -6 %)
 constexpr float kRayGrow = WR_BVH_RAY_GROW;  // x (ray length to the search bound + 1), per ray
+// A triangle whose edges from p0 are both non-zero and nearly parallel:
+// |e1 x e2| <= kSliverSin |e1| |e2| (the sine of the corner angle; wr_fast.h's
+// WR_GRAZE_REL, for every direction at once).  Triangle::hit's denominator is
+// then rounding noise for every ray, and so is the t it accepts: a hit far off
+// the triangle's grown box, which the search never visits.  build_fast
+// declines a scene that holds one (slivers).
+constexpr double kSliverSin = 1e-5;
 static_assert(kMaxLeaf >= 1 && kMaxLeaf <= 8, "leaf links hold count - 1 in 3 bits");
 
 }  // namespace wrf

@@ -576,6 +576,19 @@ __device__ __forceinline__ void kd_walk(const DevScene& S, V3 o, V3 d, float rtm
 // them: the caller walks the ray the serial way.  Node indices < 2^26 (the
 // depth shares their word) and KD depth <= 43 (the position's bits): the host
 // checks, FastScene::walk_wave.
+// A ray with a direction component whose reciprocal is not finite (zero, or a
+// denormal).  At a node split exactly at the origin's coordinate the
+// reference's t = (split - o) x (1 / d) is 0 x inf = NaN: it passes every
+// comparison of :339-340, both children are taken with a NaN bound, and below
+// a NaN tmax a plane at t = inf is pushed as a far child too -- whose pop ends
+// the walk at the :323 stop (rtmax < inf) with entries still below it.  The
+// serial kd_walk does the same, float for float; the wave walk and the
+// membership replays rest on the far entries' tmin growing down the stack, so
+// such a ray is walked the serial way (axis-parallel rays).
+__device__ __forceinline__ bool axis_ray(V3 d) {
+  const float m = 1.17549435e-38f;  // FLT_MIN
+  return !(fabsf(d.x) >= m && fabsf(d.y) >= m && fabsf(d.z) >= m);
+}
 __device__ __forceinline__ uint32_t wave_add32(uint32_t v) {
 #pragma unroll
   for (int sh = 32; sh >= 1; sh >>= 1) v += __shfl_xor(v, sh);
@@ -585,6 +598,7 @@ template <bool COUNT>
 __device__ __forceinline__ bool kd_walk_wave(const DevScene& S, V3 o, V3 d, float rtmin, float rtmax, uint32_t* lds,
                                              int words, float& t_best, int& best, FastCounters& ctr) {
   const int lane = __lane_id();
+  if (axis_ray(d)) return false;  // (wave-uniform: every lane holds the ray)
   t_best = WR_INF;
   best = -1;
   float tmin0, tmax0;
@@ -1756,7 +1770,7 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
           t3 = WR_INF;
           p1 = -1;
           p2 = -1;
-          gz = false;
+          gz = axis_ray(d);  // (the KD walk settles it: no membership replay for its NaN bounds)
           sp = 0;
           cur = 0;
           rn = rt = 0;
@@ -1770,7 +1784,7 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
           // spheres: their boxes cover Sphere::hit's rounding for origins in
           // [org_lo, org_hi] only (wr_bvh.cpp): a ray from elsewhere (an API
           // caller's) takes the KD walk
-          if (SPH) gz = !(o.x >= F.org_lo.x && o.y >= F.org_lo.y && o.z >= F.org_lo.z && o.x <= F.org_hi.x &&
+          if (SPH) gz |= !(o.x >= F.org_lo.x && o.y >= F.org_lo.y && o.z >= F.org_lo.z && o.x <= F.org_hi.x &&
                           o.y <= F.org_hi.y && o.z <= F.org_hi.z);
         }
         if (__ballot(idle && idx >= n)) pool = false;

@@ -2309,7 +2309,7 @@ int wr_create(const wr_scene* sc, int device, wr_context** out) {
 
 int wr_set_trace_mode(wr_context* c, int mode) {
   if (!c || (mode != WR_TRACE_REFERENCE && mode != WR_TRACE_BVH)) return fail(WR_E_ARG, "bad trace mode");
-  if (mode == WR_TRACE_BVH && !c->fast_ok) return fail(WR_E_SCENE, "the scene has no verified BVH (empty, or too large)");
+  if (mode == WR_TRACE_BVH && !c->fast_ok) return fail(WR_E_SCENE, "the scene has no verified BVH (empty, too large, or a triangle with nearly collinear vertices)");
   c->fast_on = mode == WR_TRACE_BVH;
   for (wr_context* d : c->subs) d->fast_on = c->fast_on;
   return WR_OK;
