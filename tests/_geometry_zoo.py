@@ -275,6 +275,28 @@ def fixture(name):
     return _fixtures[name]
 
 
+def compare(label, hits, occ, fx):
+    """The GPU tests' comparison with a fixture (test_gpu._check_golden_corpus' on a zoo fixture): primitive,
+    t bit for bit, p and n, inside, material, and the occlusion answers."""
+    bad = np.nonzero(hits["prim"] != fx["prim"])[0]
+    assert bad.size == 0, (label, "prim", int(bad.size), bad[:8].tolist(), hits["prim"][bad[:8]].tolist(),
+                           fx["prim"][bad[:8]].tolist())
+    hit = fx["prim"] >= 0
+    got = np.concatenate([hits["t"][:, None], hits["p"], hits["n"]], axis=1).astype(np.float32)
+    bad = np.nonzero(hit & (got[:, 0].view(np.uint32) != fx["vals"][:, 0].view(np.uint32)))[0]
+    assert bad.size == 0, (label, "t", int(bad.size), bad[:8].tolist(), got[bad[:4], 0], fx["vals"][bad[:4], 0])
+    # p and n: the same bits, but a zero may carry either sign and a NaN any payload (the normal of a
+    # zero-area triangle the reference reports is NaN): _check_golden_corpus' equal floats, NaN included
+    want = fx["vals"]
+    same = (got.view(np.uint32) == want.view(np.uint32)) | ((got == 0) & (want == 0)) | (np.isnan(got) & np.isnan(want))
+    bad = np.nonzero(hit & ~same.all(axis=1))[0]
+    assert bad.size == 0, (label, "p n", int(bad.size), bad[:8].tolist(), got[bad[:2]], fx["vals"][bad[:2]])
+    assert np.array_equal(hits["inside"][hit], fx["inside"][hit]), (label, "inside")
+    assert np.array_equal(hits["mat_id"][hit], fx["mat"][hit]), (label, "material")
+    bad = np.nonzero(occ != fx["occ"])[0]
+    assert bad.size == 0, (label, "occluded", int(bad.size), bad[:8].tolist())
+
+
 def brute_force_hits(name, rays):
     """t of every primitive along every ray, float64 Moeller-Trumbore and the
     sphere quadratic over all primitives ((n, nprims), inf where there is no hit

@@ -20,6 +20,7 @@ import pytest
 
 import _geometry_zoo as gz
 import _oracle
+from _geometry_zoo import compare as _compare
 from _parity import assert_film_parity, assert_ray_counts
 from test_gpu import normalize_f32
 from test_gpu_bvh import _corpus, _plane_grazing_rays, _same_hits
@@ -68,28 +69,6 @@ def zoo(request):
     yield z
     for c in z["ctx"].values():
         c.close()
-
-
-def _compare(label, hits, occ, fx):
-    """test_gpu._check_golden_corpus' comparison on a zoo fixture: primitive,
-    t bit for bit, p and n, inside, material, and the occlusion answers."""
-    bad = np.nonzero(hits["prim"] != fx["prim"])[0]
-    assert bad.size == 0, (label, "prim", int(bad.size), bad[:8].tolist(), hits["prim"][bad[:8]].tolist(),
-                           fx["prim"][bad[:8]].tolist())
-    hit = fx["prim"] >= 0
-    got = np.concatenate([hits["t"][:, None], hits["p"], hits["n"]], axis=1).astype(np.float32)
-    bad = np.nonzero(hit & (got[:, 0].view(np.uint32) != fx["vals"][:, 0].view(np.uint32)))[0]
-    assert bad.size == 0, (label, "t", int(bad.size), bad[:8].tolist(), got[bad[:4], 0], fx["vals"][bad[:4], 0])
-    # p and n: the same bits, but a zero may carry either sign and a NaN any payload (the normal of a
-    # zero-area triangle the reference reports is NaN): _check_golden_corpus' equal floats, NaN included
-    want = fx["vals"]
-    same = (got.view(np.uint32) == want.view(np.uint32)) | ((got == 0) & (want == 0)) | (np.isnan(got) & np.isnan(want))
-    bad = np.nonzero(hit & ~same.all(axis=1))[0]
-    assert bad.size == 0, (label, "p n", int(bad.size), bad[:8].tolist(), got[bad[:2]], fx["vals"][bad[:2]])
-    assert np.array_equal(hits["inside"][hit], fx["inside"][hit]), (label, "inside")
-    assert np.array_equal(hits["mat_id"][hit], fx["mat"][hit]), (label, "material")
-    bad = np.nonzero(occ != fx["occ"])[0]
-    assert bad.size == 0, (label, "occluded", int(bad.size), bad[:8].tolist())
 
 
 @pytest.mark.parametrize("mode", list(MODES))
