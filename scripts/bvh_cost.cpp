@@ -8,7 +8,7 @@
 // secondary rays from random surface points in cosine directions about either
 // side's normal (the BDPT mix is ~1/4 primaries, ~3/4 bounces).
 // Build: g++ -O2 -std=c++17 -I winmad-s-raytracer-v1.0_amd/csrc -I include
-//   scripts/bvh_cost.cpp winmad-s-raytracer-v1.0_amd/csrc/{wr_scene,wr_bvh}.cpp -lpthread
+//   -I scripts scripts/bvh_cost.cpp winmad-s-raytracer-v1.0_amd/csrc/{wr_scene,wr_bvh}.cpp -lpthread
 // Usage: bvh_cost scene [rays]
 #include <algorithm>
 #include <cmath>
@@ -19,39 +19,12 @@
 #include <string>
 #include <vector>
 
+#include "bvh_tool_common.h"
 #include "wr_bvh.h"
 #include "wr_scene.h"
 
 namespace {
-constexpr float kEps = 1e-3f;
-
-struct V {
-  float x, y, z;
-};
-V sub(V a, V b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-V add(V a, V b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-V mul(V a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-float dot(V a, V b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-V cross(V a, V b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-V norm(V a) { return mul(a, 1.f / std::sqrt(dot(a, a))); }
-V f3(wr::F3 p) { return {p.x, p.y, p.z}; }
-
-bool tri(const wrf::TriRec& r, V o, V d, float& t) {
-  const V p0{r.a[0], r.a[1], r.a[2]};
-  const V e1{-r.a[3], -r.b[0], -r.b[1]}, e2{-r.b[2], -r.b[3], -r.c[0]};
-  const V pv = cross(d, e2);
-  const float det = dot(e1, pv);
-  if (std::fabs(det) < 1e-12f) return false;
-  const float inv = 1.f / det;
-  const V tv = sub(o, p0);
-  const float u = dot(tv, pv) * inv;
-  if (u < -kEps || u > 1.f) return false;
-  const V qv = cross(tv, e1);
-  const float v = dot(d, qv) * inv;
-  if (v < -kEps || u + v > 1.f) return false;
-  t = dot(e2, qv) * inv;
-  return t > kEps;
-}
+using namespace bvhtool;  // kEps, V and its helpers, tri(), the secondary rays
 
 struct Cost {
   double nodes = 0, tests = 0;
@@ -272,14 +245,8 @@ int main(int argc, char** argv) {
   std::mt19937 rng(12345);
   std::uniform_real_distribution<float> U(0.f, 1.f);
   // area-weighted triangle pick
-  std::vector<double> cdf(s.prims.size());
-  double acc = 0;
-  for (size_t i = 0; i < s.prims.size(); ++i) {
-    const auto& p = s.prims[i];
-    acc += 0.5 * std::sqrt(dot(cross(sub(f3(p.p1), f3(p.p0)), sub(f3(p.p2), f3(p.p0))),
-                               cross(sub(f3(p.p1), f3(p.p0)), sub(f3(p.p2), f3(p.p0)))));
-    cdf[i] = acc;
-  }
+  std::vector<double> cdf;
+  const double acc = area_cdf(s, cdf);
   Cost cam, sec;
   std::vector<Wide> wides;
   for (int w : {4, 8}) wides.emplace_back(F, w);
@@ -295,21 +262,8 @@ int main(int argc, char** argv) {
     walk(F, cpos, cd, cam);
     for (size_t w = 0; w < wides.size(); ++w) wides[w].walk(cpos, cd, wcam[w], wlv[w]);
     // secondary ray: random surface point, cosine direction about a random side's normal
-    const double x = U(rng) * acc;
-    const size_t k = static_cast<size_t>(std::lower_bound(cdf.begin(), cdf.end(), x) - cdf.begin());
-    const auto& p = s.prims[std::min(k, s.prims.size() - 1)];
-    float u = U(rng), v = U(rng);
-    if (u + v > 1.f) {
-      u = 1.f - u;
-      v = 1.f - v;
-    }
-    const V e1 = sub(f3(p.p1), f3(p.p0)), e2 = sub(f3(p.p2), f3(p.p0));
-    V n = norm(cross(e1, e2));
-    if (U(rng) < 0.5f) n = mul(n, -1.f);
-    const V t1 = norm(std::fabs(n.x) > 0.5f ? cross(n, V{0, 1, 0}) : cross(n, V{1, 0, 0})), t2 = cross(n, t1);
-    const float r1 = U(rng), r2 = U(rng), rr = std::sqrt(r1), ph = 6.2831853f * r2;
-    const V dir = norm(add(mul(n, std::sqrt(1.f - r1)), add(mul(t1, rr * std::cos(ph)), mul(t2, rr * std::sin(ph)))));
-    const V org = add(add(add(f3(p.p0), mul(e1, u)), mul(e2, v)), mul(dir, kEps));
+    V org, dir;
+    secondary_ray(s, cdf, acc, rng, U, org, dir);
     walk(F, org, dir, sec);
     for (size_t w = 0; w < wides.size(); ++w) wides[w].walk(org, dir, wsec[w], wlv[w]);
   }

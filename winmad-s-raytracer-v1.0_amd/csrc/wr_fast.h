@@ -85,6 +85,11 @@ struct FastCounters {  // algorithmic work (count_work)
   // those in which a lane finished its ray, the finishing lanes (per lane), and
   // the full 64-ray settle batches (RL, per wave)
   uint32_t rounds, fin_rounds, fin_lanes, settle_full;
+  // the node loop inside those rounds (WR_BVH_SPEC; all four per wave, from
+  // ballots): its iterations, the lanes that stepped a node summed over them,
+  // the lanes that tested a leaf, and the lanes a round's end left mid-descent
+  // (kStragglerNum)
+  uint32_t node_iters, step_lanes, leaf_lanes, carried_lanes;
 };
 
 // Per wave: the stack columns, 8 bytes per entry and lane (BVH: link + entry t;
@@ -177,6 +182,23 @@ __host__ __device__ constexpr size_t search_spill_entries(int depth, int wide) {
 #ifndef WR_BVH_SPEC
 #define WR_BVH_SPEC 1
 #endif
+// When a round's node loop ends (DESIGN.md 4b "When a round ends"): once at
+// most K = (active lanes * kStragglerNum) >> kStragglerShift of the wave's
+// lanes still lack a leaf; those keep descending in the next round.  A wave
+// with fewer than kStragglerMinLanes active lanes gets K = 0 (the loop runs
+// until every lane has a leaf): drain tails and launches of few rays.
+// 1/4 (16 lanes of a full wave), measured against 0, 1/32, 1/16, 1/8 and 3/16:
+// profiles/r20/round_exit/README.md.
+#ifndef WR_STRAGGLER_NUM
+#define WR_STRAGGLER_NUM 1
+#endif
+#ifndef WR_STRAGGLER_SHIFT
+#define WR_STRAGGLER_SHIFT 2
+#endif
+constexpr int kStragglerNum = WR_STRAGGLER_NUM, kStragglerShift = WR_STRAGGLER_SHIFT;
+constexpr int kStragglerMinLanes = 16;
+static_assert(kStragglerNum >= 0 && kStragglerNum < (1 << kStragglerShift),
+              "K stays below the active lanes: every round steps at least one node-loop iteration");
 #ifndef WR_TIE_SPLIT
 #define WR_TIE_SPLIT 0  // diagnostic: time the tie resolution's phases (count_work)
 #endif
@@ -1797,15 +1819,29 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
     }
     // ---- inner nodes until this lane has a leaf (or is done).  WR_BVH_SPEC: a
     // leaf reached is parked in `pl` and the lane descends on (its next inner
-    // nodes) until every lane has parked one or finished
+    // nodes) until all but `late` lanes have parked one or finished
+    // (kStragglerNum).  Every active lane lacks a leaf when the round begins
+    // (pl == 0, and a finished lane has left) and late is below their number,
+    // so each round steps at least once.  A lane the loop leaves mid-descent
+    // keeps cur >= 0 and pl == 0 (or cur < 0, a leaf it has yet to park): the
+    // leaf phase wants pl < 0, the finish cur == kDone, the refill r < 0 --
+    // all three pass it by, and it descends on in the next round.
+#if WR_BVH_SPEC
+    const int nact = __popcll(__ballot(act));
+    const int late = nact < kStragglerMinLanes ? 0 : (nact * kStragglerNum) >> kStragglerShift;
+#endif
     for (;;) {
 #if WR_BVH_SPEC
-      if (!__ballot(act && pl >= 0 && cur != kDone)) break;
+      if (__popcll(__ballot(act && pl >= 0 && cur != kDone)) <= late) break;
       if (act && cur < 0 && pl >= 0) {
         pl = cur;
         pop();
       }
       const bool step = act && cur >= 0 && cur != kDone;
+      if (COUNT) {
+        ++ctr.node_iters;
+        ctr.step_lanes += __popcll(__ballot(step));
+      }
 #else
       const bool step = act && cur >= 0 && cur != kDone;
       if (!__ballot(step)) break;
@@ -2004,6 +2040,10 @@ __device__ __forceinline__ void trace_fast(const DevScene& S, const FastScene& F
     }
     // ---- leaf: test its triangles (Triangle::hit), keep (t1, p1) and t2
 #if WR_BVH_SPEC
+    if (COUNT) {
+      ctr.carried_lanes += __popcll(__ballot(act && pl >= 0 && cur != kDone));
+      ctr.leaf_lanes += __popcll(__ballot(act && pl < 0));
+    }
     if (act && pl < 0) {
       const int l = ~pl;
       pl = 0;

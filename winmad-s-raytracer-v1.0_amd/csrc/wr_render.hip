@@ -161,7 +161,9 @@ struct DevCounters {
   unsigned long long verify_rays, verify_bad;                   // WR_BVH_VERIFY
   unsigned long long lat[12];  // WR_TRACE_BVH latency tail (FastCounters mem_max .. scans; max or sum; tie_col .. tie_pass2)
   unsigned long long ww[4];   // kd_walk_wave: walks, rounds, nodes, serial fall-backs
-  unsigned long long rounds[4];  // the search (count_work): outer rounds, rounds with a finisher, finishing lanes, full settle batches
+  // the search (count_work): outer rounds, rounds with a finisher, finishing lanes, full settle batches;
+  // node-loop iterations, stepping lanes over them, leaf-phase lanes, lanes carried over a round's end
+  unsigned long long rounds[8];
   unsigned long long overflow;  // BDPT: appends a full vertex pool / shadow queue dropped (the render is redone)
 };
 
@@ -305,6 +307,10 @@ __device__ __forceinline__ void fast_counts(DevCounters* ctr, const FastCounters
     atomicAdd(&ctr->rounds[1], static_cast<unsigned long long>(fc.fin_rounds));
     atomicAdd(&ctr->rounds[2], fin);
     atomicAdd(&ctr->rounds[3], static_cast<unsigned long long>(fc.settle_full));
+    atomicAdd(&ctr->rounds[4], static_cast<unsigned long long>(fc.node_iters));
+    atomicAdd(&ctr->rounds[5], static_cast<unsigned long long>(fc.step_lanes));
+    atomicAdd(&ctr->rounds[6], static_cast<unsigned long long>(fc.leaf_lanes));
+    atomicAdd(&ctr->rounds[7], static_cast<unsigned long long>(fc.carried_lanes));
   }
 }
 #ifndef WR_FAST_WAVES
@@ -1484,12 +1490,14 @@ int ensure_t2(wr_context* c, Pipe& p, size_t rays) {
 // One persistent traversal launch over the queues of Q (max_rays bounds the
 // grid).  WR_TRACE_BVH: the verified-BVH search + its resolve launch instead.
 // WR_TRACE_LOG, counting launches: the search's outer rounds (DevCounters::rounds)
-static void log_rounds(const unsigned long long r[4]) {
+static void log_rounds(const unsigned long long r[8]) {
   if (r[0])
     std::fprintf(stderr,
                  "[wr bvh rounds] %llu outer rounds, %llu with a finisher (%.3f), %llu finishing lanes (%.1f per such round), "
-                 "%llu full settle batches\n",
-                 r[0], r[1], double(r[1]) / r[0], r[2], r[1] ? double(r[2]) / r[1] : 0.0, r[3]);
+                 "%llu full settle batches; %llu node-loop iterations (%.1f per round), %llu stepping lanes (%.1f per "
+                 "iteration), %llu leaf-phase lanes (%.1f per round), %llu lanes carried mid-descent\n",
+                 r[0], r[1], double(r[1]) / r[0], r[2], r[1] ? double(r[2]) / r[1] : 0.0, r[3], r[4], double(r[4]) / r[0],
+                 r[5], r[4] ? double(r[5]) / r[4] : 0.0, r[6], double(r[6]) / r[0], r[7]);
 }
 
 int trace_launch(wr_context* c, hipStream_t stream, DevCounters* ctr, const TraceSlot& ts, Timer& tm, bool count,
@@ -1840,12 +1848,12 @@ int finish_render(wr_context* c, int n, wr_stats* st, double t0_host, unsigned l
                    lat[7] * 0.01, lat[8] * 0.01, lat[9], lat[11], lat[10] * 0.01);
     std::fprintf(stderr, "[wr bvh walks] many-leaf %llu, no visited hit %llu, crowd %llu, band %llu\n", why[0], why[1],
                  why[2], why[3]);
-    unsigned long long ww[4] = {0, 0, 0, 0}, rounds[4] = {0, 0, 0, 0};
+    unsigned long long ww[4] = {0, 0, 0, 0}, rounds[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int i = 0; i < n; ++i) {
       DevCounters h;
       HIPCHK(hipMemcpy(&h, c->pipes[i].ctr, sizeof h, hipMemcpyDeviceToHost));
       for (int k = 0; k < 4; ++k) ww[k] += h.ww[k];
-      for (int k = 0; k < 4; ++k) rounds[k] += h.rounds[k];
+      for (int k = 0; k < 8; ++k) rounds[k] += h.rounds[k];
     }
     log_rounds(rounds);
     std::fprintf(stderr, "[wr bvh wave walks] %llu walks, %.1f rounds and %.1f nodes per walk, %llu serial fall-backs\n",
