@@ -636,6 +636,82 @@ int wr_points_in_radius_dev(wr_context* ctx, const wr_points* idx, const float* 
 int wr_points_knn_dev(wr_context* ctx, const wr_points* idx, const float* q, int64_t nq, int32_t k, float max_sqr_dist,
                       int32_t* index /* nq*k */, float* sqr_dist /* nq*k */, int32_t* count /* nq */);
 
+/* ---- photon mapping (PhotonIntegrator, surfaceIntegrator/photonMap.{h,cpp};
+ * DESIGN.md 15).  Callers detect these entry points by their symbols
+ * (WR_API_VERSION stays 8).  Single-device: a wr_create_multi context is
+ * refused with WR_E_ARG.
+ *
+ * wr_photon_map_build runs buildPhotonMap: shot s = 0, 1, ... draws from
+ *   counter stream (seed, 0, 3, s); the caustic map is the first n_caustic
+ *   caustic photons in (shot, bounce) order, the indirect map the first
+ *   n_indirect indirect ones; shooting ends after the first shot at which both
+ *   maps are full, else after max_shots (a map is then what was found).  The
+ *   maps are a pure function of (scene, seed, n_caustic, n_indirect,
+ *   max_path_length, max_shots): shot_batch and cell change no byte of them.
+ *   A map count of 0 asks for no map of that class.  The map belongs to the
+ *   caller (wr_photon_map_free; NULL is a no-op) and must be freed before its
+ *   context is destroyed.
+ * wr_photon_map_read copies a map's photons out, in map order: pos, wi, alpha
+ *   count*3 floats each, shot count int32 (the 0-based shot of each photon);
+ *   any pointer may be NULL; on_device: the pointers are device memory of the
+ *   context's device.
+ * wr_photon_estimate_dev is estimate() for the caller's hits (wr_hit records,
+ *   as wr_trace_closest_dev writes them) and directions wo: with k_eff =
+ *   min(k, photons with a finite d2), the k_eff photons smallest by
+ *   (d2, index); msd = max_sqr_dist * 2^j for the smallest j >= 0 with the
+ *   k_eff-th d2 < msd; scale = 1 / (PI * msd * k_eff); the terms
+ *   (brdf | alpha) * (cos * scale / pdf) added in ascending (d2, index) order,
+ *   a photon below the surface evaluated with its world z negated.  found[j] =
+ *   k_eff.  A miss, a non-finite position or an empty map gives found 0, msd 0
+ *   and black; an emitter or a hit without a BSDF gives black.
+ * wr_render_photon is SurfaceIntegrator::render over PhotonIntegrator::
+ *   raytracing: samples, streams, stratification and the film (a sum over
+ *   samples, PT layout) as wr_render_path; depths 0..2.  direct_target 0 puts
+ *   the direct-light shadow ray's target at the camera ray's hit distance, as
+ *   the reference does; 1 at the light's distance.
+ * WR_E_ARG: a null pointer the call needs; counts < 0 or above 2^24;
+ *   max_path_length outside 1..32; max_shots outside 1..2^31 - 1; shot_batch
+ *   < 0 or above 2^22; a cell that is neither 0 nor a finite number > 0; k
+ *   outside 1..64; max_sqr_dist not a finite number > 0; `which` not
+ *   WR_PHOTON_*; a map of another context; the array checks of the _dev calls
+ *   above.  WR_E_SCENE: a scene without lights.  n == 0 succeeds. */
+typedef struct {
+  int32_t n_caustic, n_indirect;  /* 10000 / 100000 in the reference                 */
+  int32_t max_path_length;        /* 5                                                */
+  int64_t max_shots;              /* 500000 (the reference never reads its own cap)  */
+  int32_t shot_batch;             /* shots per batch; 0: 65536                       */
+  float   cell;                   /* the maps' grid cell; 0: derived  */
+  uint32_t seed;
+} wr_photon_map_params;
+typedef struct wr_photon_map wr_photon_map;
+typedef struct {
+  int64_t shots;                          /* shots run                                           */
+  int32_t caustic_count, indirect_count;  /* photons in each map                                 */
+  int64_t caustic_paths, indirect_paths;  /* 1-based shot of a full map's last photon, else shots */
+  int64_t device_bytes;
+  float   caustic_cell, indirect_cell;
+} wr_photon_map_info;
+enum { WR_PHOTON_CAUSTIC = 0, WR_PHOTON_INDIRECT = 1 };
+typedef struct {
+  int32_t width, height, spp;
+  int32_t sample_begin, sample_count;  /* as wr_path_params                   */
+  int32_t knn;                         /* 50 in the reference                 */
+  float   max_sqr_dist;                /* 0.1                                 */
+  int32_t direct_target;               /* 0: the reference's shadow-ray target */
+  uint32_t seed;
+  int32_t time_kernels, count_work;    /* accepted, not used                  */
+} wr_photon_params;
+int wr_photon_map_build(wr_context* ctx, const wr_photon_map_params* p, wr_photon_map** out, wr_stats* stats);
+int wr_photon_map_info_get(const wr_photon_map* map, wr_photon_map_info* out);
+int wr_photon_map_read(wr_context* ctx, const wr_photon_map* map, int which, float* pos, float* wi, float* alpha,
+                       int32_t* shot, int on_device);
+void wr_photon_map_free(wr_photon_map* map);
+int wr_photon_estimate_dev(wr_context* ctx, const wr_photon_map* map, int which, const wr_hit* hits /* n */,
+                           const float* wo /* n*3 */, int64_t n, int32_t k, float max_sqr_dist, float* rgb /* n*3 */,
+                           float* msd /* n or NULL */, int32_t* found /* n or NULL */);
+int wr_render_photon(wr_context* ctx, const wr_photon_map* map, const wr_photon_params* p, float* film,
+                     int film_on_device, wr_stats* stats);
+
 /* ---- output (ImageFilm::outputImage, scene/film.cpp:39-64; BDPT transpose
  * bidirPathTracing.cpp:29-46) ---- scale -> clamp [0,1] -> pow(1/gamma) ->
  * (uchar)(x*255.0); binary PPM (RGB).  transpose != 0 swaps [i][j] <-> [j][i]

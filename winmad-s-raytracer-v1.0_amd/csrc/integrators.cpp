@@ -314,4 +314,53 @@ void PathIntegrator::outputImage(const char* filename) {
   ok(wr_film_write_image(film.data(), height, width, 1.f, 2.2f, 0, filename));
 }
 
+PhotonIntegrator::~PhotonIntegrator() {
+  if (map_) wr_photon_map_free(map_);  // before the base class destroys the context
+}
+
+void PhotonIntegrator::init(const char* filename, Parameters& para) {  // photonMap.cpp:7-32
+  maxTracingDepth = para.MAX_TRACING_DEPTH;
+  samplesPerPixel = para.SAMPLES_PER_PIXEL;
+  height = para.HEIGHT;
+  width = para.WIDTH;
+  reserveAtInit = false;  // wr_reserve knows no photon integrator: the render allocates
+  if (devices.size() > 1) throw std::runtime_error("winmad_rt: -pm renders on one GPU (photon maps are single-device)");
+  load(filename);
+}
+
+void PhotonIntegrator::buildPhotonMap() {
+  if (map_) wr_photon_map_free(map_);
+  map_ = nullptr;
+  wr_photon_map_params p{};
+  p.n_caustic = nCausticPhotons;
+  p.n_indirect = nIndirectPhotons;
+  p.max_path_length = maxPathLength;
+  p.max_shots = maxPhotonShot;
+  p.seed = seed;
+  ok(wr_photon_map_build(ctx_, &p, &map_, &stats));
+  ok(wr_photon_map_info_get(map_, &mapInfo));
+  nCausticPaths = static_cast<int>(mapInfo.caustic_paths);
+  nIndirectPaths = static_cast<int>(mapInfo.indirect_paths);
+}
+
+void PhotonIntegrator::render() {
+  if (checkpointPath.size()) throw std::runtime_error("winmad_rt: -pm has no checkpoint");
+  if (!map_) buildPhotonMap();
+  wr_photon_params p{};
+  p.width = width;
+  p.height = height;
+  p.spp = samplesPerPixel;
+  p.knn = knnPhotons;
+  p.max_sqr_dist = maxSqrDis;
+  p.direct_target = directTarget;
+  p.seed = seed;
+  ok(wr_render_photon(ctx_, map_, &p, film.data(), 0, &stats));
+  const float inv = 1.f / samplesPerPixel;  // film->scale(1.f / samplesPerPixel) (surfaceIntegrator.cpp:45)
+  for (float& v : film) v = v * inv;
+}
+
+void PhotonIntegrator::outputImage(const char* filename) {  // photonMap.cpp:45
+  ok(wr_film_write_image(film.data(), height, width, 1.f / 150.f, 2.2f, 0, filename));
+}
+
 }  // namespace winmad

@@ -144,4 +144,27 @@ class PathIntegrator : public SurfaceIntegrator, public Denoise {
   void raytracing(const wr_ray* rays, int64_t n, float* rgb, int sample = 0);
 };
 
+// src/surfaceIntegrator/photonMap.{h,cpp} + SurfaceIntegrator::render.  One GPU;
+// no checkpoint, error target or denoiser.  render() builds the maps first
+// if buildPhotonMap() has not been called.
+class PhotonIntegrator : public SurfaceIntegrator {
+ public:
+  int nCausticPhotons = 10000, nIndirectPhotons = 100000, knnPhotons = 50;  // photonMap.cpp:9-19
+  float maxSqrDis = 0.1f;
+  int maxPathLength = 5, maxPhotonShot = 500000;  // (the cap holds here: the reference never reads it)
+  int nCausticPaths = 0, nIndirectPaths = 0;
+  int maxTracingDepth = 7;
+  int directTarget = 0;  // 0: the reference's direct-light shadow ray (photonMap.cpp:259); 1: to the light
+  uint32_t seed = 5489;
+  wr_photon_map_info mapInfo{};
+  ~PhotonIntegrator() override;
+  void init(const char* filename, Parameters& para) override;  // :7-32
+  void buildPhotonMap();                                         // :48-162
+  void render() override;                                        // surfaceIntegrator.cpp:14-46 over :304-366
+  void outputImage(const char* filename) override;               // :34-46: scale 1 / 150, gamma 2.2
+
+ private:
+  wr_photon_map* map_ = nullptr;
+};
+
 }  // namespace winmad

@@ -1,6 +1,6 @@
 // wr_tot -- command-line twin of the reference's main() (src/main.cpp:29-97) for
 // the GPU integrators:
-//     wr_tot <scene> <out.ppm> -bpt|-vcm|-p [--params FILE] [--iterations N] [--seed S]
+//     wr_tot <scene> <out.ppm> -bpt|-vcm|-p|-pm [--params FILE] [--iterations N] [--seed S]
 //            [--device D | --gpus N | --devices D0,D1,...] [--trace bvh|reference]
 //            [--checkpoint FILE [--checkpoint-every N] [--stop-after N]] [--hw-queues N]
 //            [--target-error X [--error-every N] [--error-out map.pfm]] [--denoise FILE]
@@ -13,6 +13,10 @@
 // Prints `error <rel_stderr> after <n> iterations`; --error-out writes the
 // standard-error map.  Not for -p (its samples are strata of one grid, not
 // independent passes) and not together with --checkpoint.
+// -pm (photon mapping, main.cpp's PhotonIntegrator): [--seed S] [--photons C,I]
+// [--knn K]: the caustic and indirect map sizes (10000,100000) and the photons
+// per estimate (50); one GPU, samples per pixel from the parameter file.
+// --target-error and --denoise are for -bpt, -vcm and -p only, --checkpoint too.
 // Parameters come from src/parameters.para relative to the CWD, as in the
 // reference (main.cpp:32), unless --params is given.  Writes time.txt like
 // main.cpp:93-95 (seconds instead of clock ticks).
@@ -50,10 +54,11 @@ std::vector<int> parse_list(const char* s) {
 int main(int argc, char** argv) {
   if (argc < 4) {
     std::fprintf(stderr,
-                 "usage: %s <scene> <out.ppm> -bpt|-vcm|-p [--params F] [--iterations N] [--seed S] "
+                 "usage: %s <scene> <out.ppm> -bpt|-vcm|-p|-pm [--params F] [--iterations N] [--seed S] "
                  "[--device D | --gpus N | --devices D0,D1,..] [--trace bvh|reference] "
                  "[--checkpoint F [--checkpoint-every N] [--stop-after N]] [--hw-queues N] "
-                 "[--target-error X [--error-every N] [--error-out map.pfm]] [--denoise FILE]\n",
+                 "[--target-error X [--error-every N] [--error-out map.pfm]] [--denoise FILE] "
+                 "[-pm: --photons C,I --knn K]\n",
                  argv[0]);
     return 2;
   }
@@ -68,6 +73,9 @@ int main(int argc, char** argv) {
   std::vector<int> devices;
   unsigned seed = 5489;
   bool bvh = true;
+  std::vector<int> photons;
+  int knn = 50;
+  const bool pm = !std::strcmp(argv[3], "-pm");
   try {
     for (int i = 4; i + 1 < argc; i += 2) {
       const char* a = argv[i];
@@ -94,8 +102,15 @@ int main(int argc, char** argv) {
         if (error_every < 1) throw std::runtime_error("usage: --error-every takes a number of iterations >= 1");
       } else if (!std::strcmp(a, "--error-out")) error_out = v;
       else if (!std::strcmp(a, "--denoise")) denoise_out = v;
+      else if (!std::strcmp(a, "--photons")) photons = parse_list(v);
+      else if (!std::strcmp(a, "--knn")) knn = std::atoi(v);
       else throw std::runtime_error(std::string("unknown option ") + a);
     }
+    if (pm && (have_target || denoise_out || checkpoint))
+      throw std::runtime_error("usage: --target-error, --denoise and --checkpoint are for -bpt, -vcm and -p only, not -pm");
+    if (!pm && (!photons.empty() || knn != 50)) throw std::runtime_error("usage: --photons and --knn are for -pm");
+    if (pm && ((!photons.empty() && photons.size() != 2) || knn < 1 || knn > 64))
+      throw std::runtime_error("usage: --photons takes C,I (caustic, indirect); --knn 1..64");
     if (have_target && !std::strcmp(argv[3], "-p"))
       throw std::runtime_error("usage: --target-error is for -bpt and -vcm: the samples of -p are strata of one "
                                "grid, stopping early would leave part of each pixel unsampled");
@@ -150,6 +165,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "usage: --denoise needs at least 2 samples per pixel (the variance of one is unknown)\n");
         return 2;
       }
+    } else if (pm) {
+      auto* p = new winmad::PhotonIntegrator();
+      p->seed = seed;
+      p->knnPhotons = knn;
+      if (photons.size() == 2) p->nCausticPhotons = photons[0], p->nIndirectPhotons = photons[1];
+      integ.reset(p);
     } else {
       std::printf("error!\n");  // main.cpp:88-91
       return 1;
@@ -158,7 +179,7 @@ int main(int argc, char** argv) {
       et->errorTarget = target_error;
       et->errorCheckEvery = error_every;
     }
-    dn->denoise = denoise_out != nullptr;
+    if (dn) dn->denoise = denoise_out != nullptr;
     integ->device = device;
     integ->devices = devices;
     integ->traceMode = WR_TRACE_REFERENCE;
@@ -175,7 +196,7 @@ int main(int argc, char** argv) {
         bvh = false;
       }
     }
-    integ->reserve();  // the GPU work buffers, before the render (as init's allocations in the reference)
+    if (!pm) integ->reserve();  // the GPU work buffers, before the render (as init's allocations in the reference)
     integ->render();
     if (integ->stopped) {
       std::printf("stopped after --stop-after %d; checkpoint %s\n", stop_after, checkpoint);
@@ -198,6 +219,13 @@ int main(int argc, char** argv) {
     if (FILE* f = std::fopen("time.txt", "w")) {
       std::fprintf(f, "time = %.6f s\n", sec);
       std::fclose(f);
+    }
+    if (auto* p = dynamic_cast<winmad::PhotonIntegrator*>(integ.get())) {
+      const wr_photon_map_info& m = p->mapInfo;
+      std::printf("photon maps: %lld shots, %d caustic (%lld paths), %d indirect (%lld paths); frame in %.3f s [trace %s]\n",
+                  static_cast<long long>(m.shots), m.caustic_count, static_cast<long long>(m.caustic_paths),
+                  m.indirect_count, static_cast<long long>(m.indirect_paths), p->stats.seconds, bvh ? "bvh" : "reference");
+      return 0;
     }
     const wr_stats& s = integ->stats;
     std::printf("rays %lld (closest %lld, shadow %lld) in %.3f s: %.2f Mrays/s [trace %s, %zu GPU(s)]\n",

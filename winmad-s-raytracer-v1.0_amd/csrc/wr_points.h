@@ -345,13 +345,57 @@ __device__ __forceinline__ void pts_knn_run(PtsKnn& S, const PtsIndex& X, float 
   }
 }
 
+// The search of one query by its wave: on return S holds the winners, ascending
+// in lanes 0 .. (their number) - 1.  The caller has set S (k, lane, limit, bound
+// = limit, key = none) and checked that the query is finite and the limit > 0.
+__device__ __forceinline__ void pts_knn_search(PtsKnn& S, const PtsIndex& X, float qx, float qy, float qz) {
+  const int64_t T = int64_t(X.tmask) + 1;
+  const int cx = pts_cell(qx, X.org[0], X.cell), cy = pts_cell(qy, X.org[1], X.cell),
+            cz = pts_cell(qz, X.org[2], X.cell);
+  // Before shell s is read, the box of shell s - 1 has been.  A record
+  // outside it lies s or more cells from the query's cell on some axis, so
+  // (the query being anywhere in its cell) more than s - 1 - err cell
+  // edges away, err bounding the rounding of the two cell computations
+  // (2^-20 of the coordinates in cells); with the margin of r', every
+  // such record has d2 >= lb^2 (1 - 2^-9).
+  const float cmax = fmaxf(fmaxf(fabsf(static_cast<float>(cx)), fabsf(static_cast<float>(cy))),
+                           fabsf(static_cast<float>(cz)));
+  bool linear = false;
+  for (int s = 0;; ++s) {  // (2 s + 1)^3 <= T: s < 2^10
+    const int64_t w = 2 * int64_t(s) + 1;
+    if (w * w * w > T) {
+      linear = true;
+      break;
+    }
+    if (s > 1) {
+      const float lbc = static_cast<float>(s - 1) - (cmax + static_cast<float>(s) + 2.f) * 9.5367431640625e-7f;
+      const float lb = lbc * X.cell * 0.9990234375f;
+      const float bd2 = __uint_as_float(static_cast<uint32_t>(S.bound >> 32));
+      if (lbc > 0.f && lb * lb * 0.998046875f > bd2) break;  // nothing out there is below the bound
+    }
+    for (int dz = -s; dz <= s; ++dz)
+      for (int dy = -s; dy <= s; ++dy) {
+        if (max(abs(dy), abs(dz)) == s) {
+          pts_knn_run(S, X, qx, qy, qz, cy + dy, cz + dz, cx - s, cx + s);
+        } else {  // an inner row: its two end cells belong to this shell
+          pts_knn_run(S, X, qx, qy, qz, cy + dy, cz + dz, cx - s, cx - s);
+          pts_knn_run(S, X, qx, qy, qz, cy + dy, cz + dz, cx + s, cx + s);
+        }
+      }
+  }
+  if (linear) {  // the shells outgrew the buckets: start over, every record once
+    S.key = kPtsNone;
+    S.bound = S.limit;
+    pts_knn_range(S, X, qx, qy, qz, 0, X.nrec, true, 0, 0, 0, 0);
+  }
+}
+
 __global__ void __launch_bounds__(256) WR_NO_PK_FP32 k_pts_knn(PtsIndex X, const float* q, int64_t nq, int k,
                                                                float max_sqr_dist, int32_t* index, float* sqr_dist,
                                                                int32_t* count) {
   const int lane = __lane_id();
   const int64_t wave0 = (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = (static_cast<int64_t>(gridDim.x) * blockDim.x) >> 6;
-  const int64_t T = int64_t(X.tmask) + 1;
   for (int64_t j = wave0; j < nq; j += nwaves) {
     const float qx = q[3 * j], qy = q[3 * j + 1], qz = q[3 * j + 2];
     PtsKnn S;
@@ -359,46 +403,7 @@ __global__ void __launch_bounds__(256) WR_NO_PK_FP32 k_pts_knn(PtsIndex X, const
     S.key = kPtsNone;
     S.limit = static_cast<uint64_t>(__float_as_uint(max_sqr_dist)) << 32;  // d2 < max_sqr_dist, strictly
     S.bound = S.limit;
-    if (pts_finite3(qx, qy, qz) && max_sqr_dist > 0.f) {
-      const int cx = pts_cell(qx, X.org[0], X.cell), cy = pts_cell(qy, X.org[1], X.cell),
-                cz = pts_cell(qz, X.org[2], X.cell);
-      // Before shell s is read, the box of shell s - 1 has been.  A record
-      // outside it lies s or more cells from the query's cell on some axis, so
-      // (the query being anywhere in its cell) more than s - 1 - err cell
-      // edges away, err bounding the rounding of the two cell computations
-      // (2^-20 of the coordinates in cells); with the margin of r', every
-      // such record has d2 >= lb^2 (1 - 2^-9).
-      const float cmax = fmaxf(fmaxf(fabsf(static_cast<float>(cx)), fabsf(static_cast<float>(cy))),
-                               fabsf(static_cast<float>(cz)));
-      bool linear = false;
-      for (int s = 0;; ++s) {  // (2 s + 1)^3 <= T: s < 2^10
-        const int64_t w = 2 * int64_t(s) + 1;
-        if (w * w * w > T) {
-          linear = true;
-          break;
-        }
-        if (s > 1) {
-          const float lbc = static_cast<float>(s - 1) - (cmax + static_cast<float>(s) + 2.f) * 9.5367431640625e-7f;
-          const float lb = lbc * X.cell * 0.9990234375f;
-          const float bd2 = __uint_as_float(static_cast<uint32_t>(S.bound >> 32));
-          if (lbc > 0.f && lb * lb * 0.998046875f > bd2) break;  // nothing out there is below the bound
-        }
-        for (int dz = -s; dz <= s; ++dz)
-          for (int dy = -s; dy <= s; ++dy) {
-            if (max(abs(dy), abs(dz)) == s) {
-              pts_knn_run(S, X, qx, qy, qz, cy + dy, cz + dz, cx - s, cx + s);
-            } else {  // an inner row: its two end cells belong to this shell
-              pts_knn_run(S, X, qx, qy, qz, cy + dy, cz + dz, cx - s, cx - s);
-              pts_knn_run(S, X, qx, qy, qz, cy + dy, cz + dz, cx + s, cx + s);
-            }
-          }
-      }
-      if (linear) {  // the shells outgrew the buckets: start over, every record once
-        S.key = kPtsNone;
-        S.bound = S.limit;
-        pts_knn_range(S, X, qx, qy, qz, 0, X.nrec, true, 0, 0, 0, 0);
-      }
-    }
+    if (pts_finite3(qx, qy, qz) && max_sqr_dist > 0.f) pts_knn_search(S, X, qx, qy, qz);
     const bool have = S.key != kPtsNone;
     if (lane < k) {
       index[j * k + lane] = have ? static_cast<int32_t>(static_cast<uint32_t>(S.key)) : -1;

@@ -571,6 +571,8 @@ static_assert(sizeof(VcmGroup) <= 4000, "kernel argument block too large");
 #include "wr_shade.h"
 // =============================================================== point sets on the device
 #include "wr_points.h"
+// =============================================================== photon mapping
+#include "wr_photon.h"
 
 }  // namespace
 
@@ -852,6 +854,8 @@ struct wr_context {
   // ---- point-set indices handed out and still alive (wr_points_build_dev):
   // wr_destroy frees them
   std::vector<wr_points*> points;
+  // ---- photon maps handed out and still alive (wr_photon_map_build): wr_destroy frees them
+  std::vector<wr_photon_map*> photon_maps;
   wr_context() = default;
   wr_context(const wr_context&) = delete;
   wr_context& operator=(const wr_context&) = delete;
@@ -876,6 +880,24 @@ struct wr_points {
   int64_t buckets = 0, max_bucket = 0;
   DevBuf<float4> rec;
   DevBuf<int> start;
+};
+
+// The two maps of wr_photon_map_build (csrc/wr_photon.h), each with its
+// point-set index; [WR_PHOTON_CAUSTIC], [WR_PHOTON_INDIRECT].  Freed like a wr_points.
+struct wr_photon_map {
+  wr_context* ctx = nullptr;
+  wr_photon_map_info info{};
+  struct Side {
+    DevBuf<float> pos;    // [count][3]
+    DevBuf<float4> pay;   // [count][2] {wi, 0}, {alpha, 0}
+    DevBuf<int32_t> shot;  // [count]
+    wr_points* idx = nullptr;  // over pos (null: no photons); owned, and listed in ctx->points
+    int count = 0;
+  } side[2];
+  PmMap dev(int which) const {
+    const Side& s = side[which];
+    return PmMap{s.idx ? s.idx->X : PtsIndex{}, s.pay.p, s.idx ? s.count : 0};
+  }
 };
 
 namespace {
@@ -2343,6 +2365,8 @@ void wr_destroy(wr_context* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (Pipe& p : c->pipes)
     if (p.stream) (void)hipStreamSynchronize(p.stream);
+  for (wr_photon_map* m : c->photon_maps) delete m;  // maps the caller did not free (their indices go below)
+  c->photon_maps.clear();
   for (wr_points* x : c->points) delete x;  // indices the caller did not free
   c->points.clear();
   delete c;
@@ -4045,6 +4069,334 @@ int wr_points_knn_dev(wr_context* c, const wr_points* idx, const float* q, int64
     hipLaunchKernelGGL(k_pts_knn, dim3(g), dim3(256), 0, c->stream, idx->X, q, nq, k, max_sqr_dist, index, sqr_dist,
                        count);
   });
+}
+
+// ---- photon mapping (wr_photon_*, wr_render_photon; kernels in
+// wr_photon.h).  Everything runs on the context stream between api_order and
+// api_finish, its traversals through api_trace like the ray calls'.
+constexpr int kPhotonBatch = 65536;  // shots per batch when shot_batch is 0
+static int photon_ctx(const wr_context* c, const std::string& who) {
+  if (!c) return fail(WR_E_ARG, who + "null context");
+  if (!c->subs.empty()) return fail(WR_E_ARG, who + "photon maps and their renders are single-device: create the context with wr_create");
+  return WR_OK;
+}
+static int photon_map_arg(const wr_context* c, const wr_photon_map* map, const std::string& who) {
+  if (!map) return fail(WR_E_ARG, who + "null map");
+  if (map->ctx != c) return fail(WR_E_ARG, who + "the map belongs to another context");
+  return WR_OK;
+}
+
+// the cell of a map's grid when the caller gives none: photons lie on
+// surfaces, so about n cell^2 / extent^2 of them share a cell; 16 extent^2 / n
+// keeps that near a dozen, a k = 50 search within two or three shells
+static int photon_cell(wr_context* c, const float* dpos, int n, float* cell) {
+  std::vector<float> h(size_t(n) * 3);
+  HIPCHK(hipMemcpyAsync(h.data(), dpos, h.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  float ext = 0.f;
+  for (int a = 0; a < 3; ++a) {
+    float lo = h[a], hi = h[a];
+    for (int i = 1; i < n; ++i) lo = std::min(lo, h[size_t(i) * 3 + a]), hi = std::max(hi, h[size_t(i) * 3 + a]);
+    ext = std::max(ext, hi - lo);
+  }
+  const float v = ext * std::sqrt(16.f / static_cast<float>(n));
+  *cell = (v > 0.f && std::isfinite(v)) ? v : 1.f;
+  return WR_OK;
+}
+
+int wr_photon_map_build(wr_context* c, const wr_photon_map_params* prm, wr_photon_map** out, wr_stats* st) {
+  const std::string who = "wr_photon_map_build: ";
+  if (int rc = photon_ctx(c, who)) return rc;
+  if (!prm || !out) return fail(WR_E_ARG, who + "null argument");
+  *out = nullptr;
+  const int cap[2] = {prm->n_caustic, prm->n_indirect};
+  if (cap[0] < 0 || cap[1] < 0 || cap[0] > (1 << 24) || cap[1] > (1 << 24))
+    return fail(WR_E_ARG, who + "n_caustic and n_indirect must be 0 .. 2^24");
+  if (prm->max_path_length < 1 || prm->max_path_length > 32) return fail(WR_E_ARG, who + "max_path_length must be 1..32");
+  if (prm->max_shots < 1 || prm->max_shots > 2147483647ll) return fail(WR_E_ARG, who + "max_shots must be 1 .. 2^31 - 1");
+  if (prm->shot_batch < 0 || prm->shot_batch > (1 << 22)) return fail(WR_E_ARG, who + "shot_batch must be 0 .. 2^22");
+  if (!(prm->cell >= 0.f) || !std::isfinite(prm->cell)) return fail(WR_E_ARG, who + "cell must be 0 or a finite number > 0");
+  if (c->ds.nlights <= 0) return fail(WR_E_SCENE, who + "the scene has no area light");
+  DeviceGuard dg;
+  if (int rc = api_order(c)) return rc;
+  const double t0 = host_now();
+  const hipStream_t sm = c->stream;
+  const int L = prm->max_path_length;
+  const int B = static_cast<int>(std::min<int64_t>(prm->shot_batch ? prm->shot_batch : kPhotonBatch, prm->max_shots));
+  const int nslot = B * L;
+  std::unique_ptr<wr_photon_map> M(new wr_photon_map);
+  M->ctx = c;
+  for (int w = 0; w < 2; ++w)
+    if (cap[w]) {
+      if (int rc = M->side[w].pos.grow(size_t(cap[w]) * 3)) return rc;
+      if (int rc = M->side[w].pay.grow(size_t(cap[w]) * 2)) return rc;
+      if (int rc = M->side[w].shot.grow(size_t(cap[w]))) return rc;
+    }
+  // the batch's work block
+  size_t scan_bytes = 0;
+  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, static_cast<const int*>(nullptr),
+                                          static_cast<int*>(nullptr), nslot + 1, sm));
+  PhBuf T{};
+  int *fc = nullptr, *fi = nullptr, *pc = nullptr, *pi = nullptr;
+  char* scan_tmp = nullptr;
+  const auto layout = [&](Arena& a) {
+    const size_t sB = B, sS = nslot;
+    T.B = B, T.L = L;
+    T.alpha = a.take<float>(3 * sB);
+    T.spec = a.take<int>(sB);
+    T.ctr = a.take<uint32_t>(sB);
+    for (int q = 0; q < 2; ++q) {
+      T.q_o[q] = a.take<float>(3 * sB);
+      T.q_d[q] = a.take<float>(3 * sB);
+      T.q_t[q] = a.take<float>(sB);
+      T.q_prim[q] = a.take<int>(sB);
+      T.q_shot[q] = a.take<int>(sB);
+    }
+    T.qn = a.take<int>(size_t(L) + 2);
+    T.s_pos = a.take<float>(3 * sS);
+    T.s_wi = a.take<float>(3 * sS);
+    T.s_alpha = a.take<float>(3 * sS);
+    T.s_class = a.take<int>(sS);
+    fc = a.take<int>(sS + 1), fi = a.take<int>(sS + 1), pc = a.take<int>(sS + 1), pi = a.take<int>(sS + 1);
+    scan_tmp = a.take<char>(std::max<size_t>(scan_bytes, 1));
+  };
+  Arena work;
+  if (int rc = work.reserve(measure(layout))) return rc;
+  layout(work);
+  int64_t s0 = 0, paths[2] = {0, 0};
+  bool full[2] = {cap[0] == 0, cap[1] == 0};
+  int count[2] = {0, 0};
+  while (s0 < prm->max_shots && !(full[0] && full[1])) {
+    const int n = static_cast<int>(std::min<int64_t>(B, prm->max_shots - s0));
+    HIPCHK(hipMemsetAsync(T.qn, 0, (size_t(L) + 2) * sizeof(int), sm));
+    HIPCHK(hipMemsetAsync(T.s_class, 0, size_t(nslot) * sizeof(int), sm));
+    const int g = std::max(1, std::min(c->grid, (n + 255) / 256));
+    hipLaunchKernelGGL(k_ph_gen, dim3(g), dim3(256), 0, sm, c->ds, T, prm->seed, s0, n);
+    for (int b = 0; b <= L; ++b) {  // nIntersections = b + 1 <= max_path_length + 1
+      const int q = b & 1;
+      if (int rc = api_trace(c, rq(T.q_o[q], T.q_d[q], B, &T.qn[b], T.q_t[q], T.q_prim[q]), size_t(B), false, TRACE_PLAIN))
+        return rc;
+      hipLaunchKernelGGL(k_ph_shade, dim3(g), dim3(256), 0, sm, c->ds, T, prm->seed, s0, b, L);
+    }
+    // the photons of each class in (shot, bounce) order: prefix sums over the slots, no atomics
+    const int gs = std::max(1, std::min(c->grid, (nslot + 256) / 256));
+    hipLaunchKernelGGL(k_ph_flags, dim3(gs), dim3(256), 0, sm, T.s_class, nslot, fc, fi);
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, fc, pc, nslot + 1, sm));
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, fi, pi, nslot + 1, sm));
+    const PhMapOut oc{M->side[0].pos.p, M->side[0].pay.p, M->side[0].shot.p, count[0], cap[0]};
+    const PhMapOut oi{M->side[1].pos.p, M->side[1].pay.p, M->side[1].shot.p, count[1], cap[1]};
+    hipLaunchKernelGGL(k_ph_scatter, dim3(gs), dim3(256), 0, sm, T, nslot, pc, pi, s0, oc, oi);
+    HIPCHK(hipGetLastError());
+    int total[2] = {0, 0};  // the two counters the host decides by
+    HIPCHK(hipMemcpyAsync(&total[0], pc + nslot, sizeof(int), hipMemcpyDeviceToHost, sm));
+    HIPCHK(hipMemcpyAsync(&total[1], pi + nslot, sizeof(int), hipMemcpyDeviceToHost, sm));
+    HIPCHK(hipStreamSynchronize(sm));
+    for (int w = 0; w < 2; ++w) {
+      if (full[w]) continue;
+      count[w] = static_cast<int>(std::min<int64_t>(cap[w], int64_t(count[w]) + total[w]));
+      if (count[w] == cap[w]) {  // the shot that stored the map's last photon (:107, :120)
+        int32_t last = 0;
+        HIPCHK(hipMemcpy(&last, M->side[w].shot.p + (cap[w] - 1), sizeof last, hipMemcpyDeviceToHost));
+        full[w] = true;
+        paths[w] = int64_t(last) + 1;
+      }
+    }
+    s0 += n;
+  }
+  // the serial loop stops after the shot that filled the second map
+  const int64_t shots = (full[0] && full[1]) ? std::min(s0, std::max(paths[0], paths[1])) : s0;
+  work.release();
+  wr_photon_map_info& I = M->info;
+  I.shots = shots;
+  I.caustic_count = count[0], I.indirect_count = count[1];
+  I.caustic_paths = (full[0] && cap[0]) ? paths[0] : shots;
+  I.indirect_paths = (full[1] && cap[1]) ? paths[1] : shots;
+  float cells[2] = {0.f, 0.f};
+  for (int w = 0; w < 2; ++w) {
+    wr_photon_map::Side& s = M->side[w];
+    s.count = count[w];
+    I.device_bytes += static_cast<int64_t>(s.pos.n * 4 + s.pay.n * 16 + s.shot.n * 4);
+    if (!count[w]) continue;
+    float cell = prm->cell;
+    if (!(cell > 0.f))
+      if (int rc = photon_cell(c, s.pos.p, count[w], &cell)) return rc;
+    if (int rc = wr_points_build_dev(c, s.pos.p, count[w], cell, &s.idx)) {
+      for (int v = 0; v < w; ++v) wr_points_free(M->side[v].idx);
+      return rc;
+    }
+    wr_points_info pinfo;
+    (void)wr_points_info_get(s.idx, &pinfo);
+    I.device_bytes += pinfo.device_bytes;
+    cells[w] = cell;
+  }
+  I.caustic_cell = cells[0], I.indirect_cell = cells[1];
+  if (st) {
+    *st = wr_stats{};
+    st->seconds = host_now() - t0;
+    st->pipelines = 1;
+  }
+  c->photon_maps.push_back(M.get());
+  *out = M.release();
+  return WR_OK;
+}
+
+int wr_photon_map_info_get(const wr_photon_map* map, wr_photon_map_info* out) {
+  if (!map || !out) return fail(WR_E_ARG, "wr_photon_map_info_get: null argument");
+  *out = map->info;
+  return WR_OK;
+}
+
+void wr_photon_map_free(wr_photon_map* map) {
+  if (!map) return;
+  wr_context* c = map->ctx;
+  for (int w = 0; w < 2; ++w) wr_points_free(map->side[w].idx);
+  DeviceGuard dg;
+  (void)hipSetDevice(c->device);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  c->photon_maps.erase(std::remove(c->photon_maps.begin(), c->photon_maps.end(), map), c->photon_maps.end());
+  delete map;
+}
+
+int wr_photon_map_read(wr_context* c, const wr_photon_map* map, int which, float* pos, float* wi, float* alpha,
+                       int32_t* shot, int on_device) {
+  const std::string who = "wr_photon_map_read: ";
+  if (int rc = photon_ctx(c, who)) return rc;
+  if (int rc = photon_map_arg(c, map, who)) return rc;
+  if (which != WR_PHOTON_CAUSTIC && which != WR_PHOTON_INDIRECT) return fail(WR_E_ARG, who + "which must be WR_PHOTON_*");
+  const wr_photon_map::Side& s = map->side[which];
+  const size_t n = static_cast<size_t>(s.count);
+  if (!n) return WR_OK;
+  if (on_device)
+    if (int rc = check_dev_args(c, "wr_photon_map_read",
+                                {wr::out(pos, n * 12, "pos", 4, true), wr::out(wi, n * 12, "wi", 4, true),
+                                 wr::out(alpha, n * 12, "alpha", 4, true), wr::out(shot, n * 4, "shot", 4, true)},
+                                "wr_photon_map_read with on_device = 0"))
+      return rc;
+  DeviceGuard dg;
+  if (int rc = api_order(c)) return rc;
+  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (pos) HIPCHK(hipMemcpyAsync(pos, s.pos.p, n * 12, kind, c->stream));
+  if (shot) HIPCHK(hipMemcpyAsync(shot, s.shot.p, n * 4, kind, c->stream));
+  if (wi) HIPCHK(hipMemcpy2DAsync(wi, 12, s.pay.p, 32, 12, n, kind, c->stream));
+  if (alpha) HIPCHK(hipMemcpy2DAsync(alpha, 12, s.pay.p + 1, 32, 12, n, kind, c->stream));
+  return api_finish(c);
+}
+
+static void gather_launch(wr_context* c, const PmMap& M, const wr_hit* hits, const float* wo, int64_t n,
+                          const int* n_dev, int k, float msd, float* rgb, float* msd_out, int32_t* found,
+                          const float* weight, const int* pix, float* film) {
+  const int g = static_cast<int>(std::min<int64_t>((n + 3) / 4, n_dev ? 16384 : (int64_t(1) << 26)));  // a wave per query
+  hipLaunchKernelGGL(k_pm_gather, dim3(std::max(1, g)), dim3(256), 0, c->stream, c->ds, c->nmats, M, hits, wo, n, n_dev,
+                     k, msd, rgb, msd_out, found, weight, pix, film);
+}
+
+int wr_photon_estimate_dev(wr_context* c, const wr_photon_map* map, int which, const wr_hit* hits, const float* wo,
+                           int64_t n, int32_t k, float max_sqr_dist, float* rgb, float* msd, int32_t* found) {
+  const std::string who = "wr_photon_estimate_dev: ";
+  if (int rc = photon_ctx(c, who)) return rc;
+  if (n < 0) return fail(WR_E_ARG, who + "n < 0");
+  if (int rc = photon_map_arg(c, map, who)) return rc;
+  if (which != WR_PHOTON_CAUSTIC && which != WR_PHOTON_INDIRECT) return fail(WR_E_ARG, who + "which must be WR_PHOTON_*");
+  if (k < 1 || k > 64) return fail(WR_E_ARG, who + "k must be 1..64");
+  if (!(max_sqr_dist > 0.f) || !std::isfinite(max_sqr_dist)) return fail(WR_E_ARG, who + "max_sqr_dist must be a finite number > 0");
+  if (n > (int64_t(1) << 28)) return fail(WR_E_ARG, who + "at most 2^28 queries per call");
+  const size_t nb = static_cast<size_t>(n);
+  if (n == 0) return WR_OK;
+  if (int rc = check_dev_args(c, "wr_photon_estimate_dev",
+                              {wr::in(hits, nb * sizeof(wr_hit), "hits", 4), wr::in(wo, nb * 12, "wo", 4),
+                               wr::out(rgb, nb * 12, "rgb", 4), wr::out(msd, nb * 4, "msd", 4, true),
+                               wr::out(found, nb * 4, "found", 4, true)},
+                              "no photon call: copy it to the device"))
+    return rc;
+  DeviceGuard dg;
+  if (int rc = api_order(c)) return rc;
+  gather_launch(c, map->dev(which), hits, wo, n, nullptr, k, max_sqr_dist, rgb, msd, found, nullptr, nullptr, nullptr);
+  return api_finish(c);
+}
+
+int wr_render_photon(wr_context* c, const wr_photon_map* map, const wr_photon_params* prm, float* film,
+                     int film_on_device, wr_stats* st) {
+  const std::string who = "wr_render_photon: ";
+  if (int rc = photon_ctx(c, who)) return rc;
+  if (int rc = photon_map_arg(c, map, who)) return rc;
+  if (!prm || !film) return fail(WR_E_ARG, who + "null argument");
+  if (prm->width <= 0 || prm->height <= 0 || prm->spp <= 0) return fail(WR_E_ARG, who + "bad film size / spp");
+  if (static_cast<int64_t>(prm->width) * prm->height > (int64_t(1) << 26)) return fail(WR_E_ARG, who + "film too large (2^26 pixels)");
+  if (prm->sample_begin < 0 || prm->sample_count < 0 || prm->sample_begin > prm->spp ||
+      static_cast<int64_t>(prm->sample_begin) + prm->sample_count > prm->spp)
+    return fail(WR_E_ARG, who + "samples [sample_begin, sample_begin + sample_count) must lie in [0, spp)");
+  if (prm->knn < 1 || prm->knn > 64) return fail(WR_E_ARG, who + "knn must be 1..64");
+  if (!(prm->max_sqr_dist > 0.f) || !std::isfinite(prm->max_sqr_dist))
+    return fail(WR_E_ARG, who + "max_sqr_dist must be a finite number > 0");
+  if (c->ds.nlights <= 0) return fail(WR_E_SCENE, who + "the scene has no area light");
+  const int P = prm->width * prm->height;
+  const size_t nf = size_t(P) * 3;
+  if (film_on_device)
+    if (int rc = check_dev_args(c, "wr_render_photon", {wr::out(film, nf * 4, "film", 4)}, "film_on_device = 0")) return rc;
+  DeviceGuard dg;
+  if (int rc = api_order(c)) return rc;
+  const double t0 = host_now();
+  const hipStream_t sm = c->stream;
+  PtBuf T{};
+  PmGq GQ{};
+  StepCounters* sc = nullptr;
+  const auto layout = [&](Arena& a) {
+    layout_pt(a, T, P);
+    GQ.hits = a.take<wr_hit>(size_t(P));
+    GQ.wo = a.take<float>(nf);
+    GQ.weight = a.take<float>(nf);
+    GQ.pix = a.take<int>(size_t(P));
+    sc = a.take<StepCounters>(1);
+  };
+  Arena work;
+  if (int rc = work.reserve(measure(layout))) return rc;
+  layout(work);
+  float* dfilm = nullptr;
+  if (int rc = film_target(c, film, film_on_device, nf, &dfilm)) return rc;
+  PtGroup GA;
+  PtArgs& A = GA.a[0];
+  A.S = c->ds;
+  A.T = T;
+  A.ctr = c->ctr;
+  A.sc = sc;
+  A.film = dfilm;
+  A.W = prm->width;
+  A.H = prm->height;
+  A.P = P;
+  A.spp = prm->spp;
+  A.grid_len = static_cast<int>(std::sqrt(static_cast<double>(prm->spp)));
+  A.max_depth = 2;
+  A.seed = prm->seed;
+  const PmMap maps[2] = {map->dev(WR_PHOTON_INDIRECT), map->dev(WR_PHOTON_CAUSTIC)};  // the order their terms are added in
+  const int k0 = prm->sample_begin, k1 = prm->sample_count > 0 ? k0 + prm->sample_count : prm->spp;
+  const int g = shade_grid(c, P);
+  for (int k = k0; k < k1; ++k) {
+    A.k = static_cast<uint32_t>(k);
+    HIPCHK(hipMemsetAsync(sc, 0, sizeof(StepCounters), sm));
+    hipLaunchKernelGGL(k_pt_gen, dim3(g, 1), dim3(kShadeBlock), 0, sm, GA);
+    for (int depth = 0; depth <= 2; ++depth) {
+      const int q = depth & 1;
+      if (int rc = api_trace(c, rq(T.q_o[q], T.q_d[q], P, &sc->ext[depth], T.q_t[q], T.q_prim[q]), size_t(P), false,
+                             TRACE_PLAIN))
+        return rc;
+      hipLaunchKernelGGL(k_pm_shade, dim3(g), dim3(kShadeBlock), 0, sm, GA, depth, GQ, prm->direct_target);
+      // the three terms in the reference's order: direct light, the indirect map, the caustic map
+      const PtBuf::Sq& Q = T.sq[(depth + 1) & 1];
+      if (int rc = api_trace(c, rq(Q.o, Q.d, P, &sc->sq[depth + 1], Q.t, Q.prim, Q.cut), size_t(P), false, TRACE_CUT))
+        return rc;
+      hipLaunchKernelGGL(k_pt_step, dim3(g, 1), dim3(kShadeBlock), 0, sm, GA, depth + 1, g, 0);
+      for (const PmMap& M : maps)
+        gather_launch(c, M, GQ.hits, GQ.wo, P, &sc->mq[depth], prm->knn, prm->max_sqr_dist, nullptr, nullptr, nullptr,
+                      GQ.weight, GQ.pix, dfilm);
+    }
+  }
+  if (int rc = api_finish(c)) return rc;
+  if (st) {
+    *st = wr_stats{};
+    st->seconds = host_now() - t0;
+    st->pipelines = 1;
+  }
+  return film_return(c, film, film_on_device, nf);
 }
 
 int wr_create_multi(const wr_scene* sc, const int* devices, int n, wr_context** out) {

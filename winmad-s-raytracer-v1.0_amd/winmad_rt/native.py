@@ -31,7 +31,9 @@ EXPORTS = ["wr_scene_load", "wr_scene_from_desc", "wr_scene_info_get", "wr_scene
            "wr_bsdf_eval_dev", "wr_bsdf_sample_dev", "wr_light_illuminate_dev", "wr_light_emit_dev",
            "wr_light_radiance_dev", "wr_rng_uniform_dev",
            "wr_points_build_dev", "wr_points_info_get", "wr_points_free", "wr_points_count_dev",
-           "wr_points_in_radius_dev", "wr_points_knn_dev"]
+           "wr_points_in_radius_dev", "wr_points_knn_dev",
+           "wr_photon_map_build", "wr_photon_map_info_get", "wr_photon_map_read", "wr_photon_map_free",
+           "wr_photon_estimate_dev", "wr_render_photon"]
 CKPT_BDPT, CKPT_VCM, CKPT_PT = 1, 2, 3
 FILM_PT, FILM_BDPT = 0, 1
 
@@ -125,6 +127,27 @@ class WrDenoiseParams(C.Structure):
 class WrPointsInfo(C.Structure):
     _fields_ = [("n", C.c_int64), ("cell", C.c_float), ("origin", C.c_float * 3), ("buckets", C.c_int64),
                 ("max_bucket", C.c_int64), ("device_bytes", C.c_int64)]
+
+
+class WrPhotonMapParams(C.Structure):
+    _fields_ = [("n_caustic", C.c_int32), ("n_indirect", C.c_int32), ("max_path_length", C.c_int32),
+                ("max_shots", C.c_int64), ("shot_batch", C.c_int32), ("cell", C.c_float), ("seed", C.c_uint32)]
+
+
+class WrPhotonMapInfo(C.Structure):
+    _fields_ = [("shots", C.c_int64), ("caustic_count", C.c_int32), ("indirect_count", C.c_int32),
+                ("caustic_paths", C.c_int64), ("indirect_paths", C.c_int64), ("device_bytes", C.c_int64),
+                ("caustic_cell", C.c_float), ("indirect_cell", C.c_float)]
+
+
+class WrPhotonParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32), ("sample_begin", C.c_int32),
+                ("sample_count", C.c_int32), ("knn", C.c_int32), ("max_sqr_dist", C.c_float),
+                ("direct_target", C.c_int32), ("seed", C.c_uint32), ("time_kernels", C.c_int32),
+                ("count_work", C.c_int32)]
+
+
+PHOTON_CAUSTIC, PHOTON_INDIRECT = 0, 1
 
 
 class WrError(RuntimeError):
@@ -241,6 +264,13 @@ def lib():
         L.wr_points_count_dev.argtypes = [P, P, P, I64, C.c_float, P, P]
         L.wr_points_in_radius_dev.argtypes = [P, P, P, I64, C.c_float, P, P, I64, P]
         L.wr_points_knn_dev.argtypes = [P, P, P, I64, C.c_int32, C.c_float, P, P, P]
+        L.wr_photon_map_build.argtypes = [P, C.POINTER(WrPhotonMapParams), C.POINTER(P), C.POINTER(WrStats)]
+        L.wr_photon_map_info_get.argtypes = [P, C.POINTER(WrPhotonMapInfo)]
+        L.wr_photon_map_read.argtypes = [P, P, I, P, P, P, P, I]
+        L.wr_photon_map_free.argtypes = [P]
+        L.wr_photon_map_free.restype = None
+        L.wr_photon_estimate_dev.argtypes = [P, P, I, P, P, I64, C.c_int32, C.c_float, P, P, P]
+        L.wr_render_photon.argtypes = [P, P, C.POINTER(WrPhotonParams), P, I, C.POINTER(WrStats)]
         L.wr_last_error.restype = C.c_char_p
         _lib = L
     return _lib
@@ -737,6 +767,26 @@ class Context:
         the context's close closes the indices it handed out."""
         return PointsIndex(self, pos, cell)
 
+    # ---- photon mapping (wr_photon_*, wr_render_photon; DESIGN.md 15)
+    def photon_map(self, n_caustic=10000, n_indirect=100000, max_path_length=5, max_shots=500000, shot_batch=0,
+                   cell=0.0, seed=5489):
+        """wr_photon_map_build: PhotonIntegrator::buildPhotonMap.  Returns a
+        PhotonMap; close it (or leave a `with` block) before the context."""
+        return PhotonMap(self, n_caustic, n_indirect, max_path_length, max_shots, shot_batch, cell, seed)
+
+    def render_photon(self, pmap, width, height, spp, knn=50, max_sqr_dist=0.1, direct_target=0, seed=5489,
+                      sample_begin=0, sample_count=0, film=None, film_ptr=None):
+        """SurfaceIntegrator::render + PhotonIntegrator::raytracing with the maps
+        of pmap (film = SUM over samples, as render_path)."""
+        p = WrPhotonParams(width, height, spp, sample_begin, sample_count, knn, max_sqr_dist, direct_target, seed, 0, 0)
+        st = WrStats()
+        if film_ptr is not None:
+            check(lib().wr_render_photon(self.h, pmap.h, C.byref(p), C.c_void_p(film_ptr), 1, C.byref(st)))
+            return None, st
+        film = _host_film(film, height, width)
+        check(lib().wr_render_photon(self.h, pmap.h, C.byref(p), film.ctypes.data_as(C.c_void_p), 0, C.byref(st)))
+        return film, st
+
     def render_bdpt(self, width, height, iterations=1, seed=5489, iter_begin=0, control_length=3,
                     max_path_length=10, faithful=1, time_kernels=0, count_work=0, film=None, film_ptr=None):
         """BidirPathTracing::render.  Host film (numpy, accumulated) or a device
@@ -995,6 +1045,84 @@ class PointsIndex:
                                       C.c_void_p(index.data_ptr()), C.c_void_p(sqr.data_ptr()),
                                       C.c_void_p(cnt.data_ptr())))
         return index, sqr, cnt
+
+
+class PhotonMap:
+    """The caustic and indirect photon maps of one photon pass (include/
+    winmad_rt.h wr_photon_*), on the context's device; a context manager."""
+
+    def __init__(self, ctx, n_caustic, n_indirect, max_path_length, max_shots, shot_batch, cell, seed):
+        self.h = None
+        self.ctx = ctx
+        p = WrPhotonMapParams(n_caustic, n_indirect, max_path_length, max_shots, shot_batch, float(cell), seed)
+        h = C.c_void_p()
+        self.stats = WrStats()
+        check(lib().wr_photon_map_build(ctx.h, C.byref(p), C.byref(h), C.byref(self.stats)))
+        self.h = h
+        if not hasattr(ctx, "_points"):
+            ctx._points = []
+        ctx._points.append(self)  # closed with the context, like its point-set indices
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().wr_photon_map_free(self.h)
+            self.h = None
+            self.ctx._points.remove(self)
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        out = WrPhotonMapInfo()
+        check(lib().wr_photon_map_info_get(self.h, C.byref(out)))
+        return {k: getattr(out, k) for k, _ in out._fields_}
+
+    def count(self, which):
+        return self.info()["indirect_count" if which == PHOTON_INDIRECT else "caustic_count"]
+
+    def photons(self, which):
+        """The photons of a map as numpy arrays: pos, wi, alpha (n, 3) float32 and shot (n,) int32."""
+        n = self.count(which)
+        a = {"pos": np.zeros((n, 3), np.float32), "wi": np.zeros((n, 3), np.float32),
+             "alpha": np.zeros((n, 3), np.float32), "shot": np.zeros((n,), np.int32)}
+        check(lib().wr_photon_map_read(self.ctx.h, self.h, which, *[a[k].ctypes.data_as(C.c_void_p) for k in
+                                                                    ("pos", "wi", "alpha", "shot")], 0))
+        return a
+
+    def photons_t(self, which):
+        """photons() as torch tensors on the context's device (nothing crosses to the host)."""
+        import torch
+        n = self.count(which)
+        dev = f"cuda:{self.ctx.devices()[0]}"
+        a = {"pos": torch.zeros((n, 3), dtype=torch.float32, device=dev),
+             "wi": torch.zeros((n, 3), dtype=torch.float32, device=dev),
+             "alpha": torch.zeros((n, 3), dtype=torch.float32, device=dev),
+             "shot": torch.zeros((n,), dtype=torch.int32, device=dev)}
+        _join_side_stream(self.ctx.devices()[0])
+        check(lib().wr_photon_map_read(self.ctx.h, self.h, which, *[C.c_void_p(a[k].data_ptr()) for k in
+                                                                    ("pos", "wi", "alpha", "shot")], 1))
+        return a
+
+    def estimate_t(self, which, hits, wo, k=50, max_sqr_dist=0.1):
+        """wr_photon_estimate_dev: estimate() at hits ((n, 10) int32 wr_hit
+        records) seen from wo ((n, 3) float32).  Returns rgb (n, 3) float32,
+        msd (n,) float32 and found (n,) int32."""
+        import torch
+        _dev_tensor(hits, "hits", (None, 10), "int32", None)
+        n = hits.shape[0]
+        rgb = torch.zeros((n, 3), dtype=torch.float32, device=hits.device)
+        msd = torch.zeros((n,), dtype=torch.float32, device=hits.device)
+        found = torch.zeros((n,), dtype=torch.int32, device=hits.device)
+        self.ctx._dev_args((hits, "hits", (n, 10), "int32"), (wo, "wo", (n, 3), "float32"))
+        check(lib().wr_photon_estimate_dev(self.ctx.h, self.h, which, C.c_void_p(hits.data_ptr()),
+                                           C.c_void_p(wo.data_ptr()), n, k, max_sqr_dist, C.c_void_p(rgb.data_ptr()),
+                                           C.c_void_p(msd.data_ptr()), C.c_void_p(found.data_ptr())))
+        return rgb, msd, found
 
 
 def film_denoise(film, film_sq, n_passes, normal=None, position=None, albedo=None, **params):
